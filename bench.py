@@ -2,7 +2,11 @@
 """bench.py -- the hot path of BASELINE.json measured on MI355X.
 
     python bench.py --gpus 1 --steps K --warmup W          # headline: HELL fp64 SpMV (configs[1])
+    python bench.py --gpus 1 --steps K --warmup W --full   # + parity, blocks, variants, other types / configs, CPU baseline
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # row-sharded SpMM
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...); everything
+else it measures or checks runs only with --full.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 A "step" is one pass of the hot path over the synthetic input, inputs resident in HBM:
   N == 1 : one spgpuDhellspmv on BASELINE configs[1] (10 M rows, 32 nnz/row uniform, hackSize 32, fp64)
@@ -36,7 +40,12 @@ def parse():
     p.add_argument("--nnz-per-row", type=int, default=32)
     p.add_argument("--pattern", default="banded", choices=["banded", "random", "window"],
                    help="column pattern of the headline workload (SURVEY 8(d) C2 defines banded and random)")
-    p.add_argument("--no-extras", action="store_true", help="skip the untimed extra variants and the CPU baseline")
+    p.add_argument("--full", action="store_true",
+                   help="beyond the timed steps: the oracle parity check, the timed blocks with the card's state, the untimed extra "
+                        "variants, other types and configurations, the CPU baseline and the counted HBM traffic (a plain run: the steps only)")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extra variants and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work budget of the cpu_baseline leg")
     p.add_argument("--workload", default="auto", choices=["auto", "spmv", "spmm"],
                    help="auto: spmv on 1 GPU (the headline metric), row-sharded spmm on more")
@@ -172,6 +181,28 @@ def time_launches(stream, fn, steps):
         stop.record(stream)
     stop.synchronize()
     return start.elapsed_time(stop) * 1e-3
+
+
+DUMP_VALUES = 1 << 21   # --dump-outputs: values written per output (16 MB in fp64); a larger output is sampled by rows
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: every device tensor of `outputs` (rows first, float32 or float64) as DIR/<name>.npy.  An output of more
+    than DUMP_VALUES values is sampled by rows: rows (i * 2654435761) mod n for i < DUMP_VALUES / values per row, ascending
+    (distinct: the multiplier is a prime above any row count), their numbers beside it as DIR/<name>_rows.npy.  The inputs are
+    seeded, so the same arguments give the same files from run to run and from one build to the next."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    for name, t in outputs.items():
+        assert t.dtype in (torch.float32, torch.float64), f"{name}: {t.dtype} is not float32 / float64"
+        rows = t.shape[0]
+        per_row = max(1, t[0].numel()) if rows else 1
+        if t.numel() > DUMP_VALUES:
+            pick = np.sort(np.arange(max(1, DUMP_VALUES // per_row), dtype=np.int64) * 2654435761 % rows)
+            np.save(os.path.join(directory, f"{name}_rows.npy"), pick.astype(np.float64))
+            t = t.index_select(0, torch.from_numpy(pick).to(t.device))
+        np.save(os.path.join(directory, f"{name}.npy"), t.cpu().numpy())
 
 
 def spot_check_hell(h, x, y, z, alpha, beta, rows_per_probe=2048):
@@ -754,19 +785,12 @@ def run_spmv(args, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(z=z))     # z of the last timed step
+
     flops = 2.0 * h["nnz"]
     alg = hell_algorithmic_bytes(h["nnz"], h["rows"], h["cols"], hacks)
     per_launch = kernel_s / args.steps
-    # the same launches once more in five blocks, with what the card reports about itself sampled beside them: a memory-bound
-    # kernel on this pool runs at speeds several per cent apart from card to card and from one set of allocations to the next
-    #  -- the record says which card, in which state, and how much the blocks differ
-    from spgpu_amd import gpu_state
-    card = gpu_state.Card(torch.cuda.current_device())
-    with gpu_state.Sampler(card) as sampler:
-        blocks = [time_launches(stream, step, max(args.steps // 5, 10)) / max(args.steps // 5, 10) * 1e3 for _ in range(5)]
-    device = dict(card.identity(), name=torch.cuda.get_device_name(dev), during_timed_blocks=sampler.summary(),
-                  note="sysfs of the card as this container sees it (clocks / power sampled every 4 ms during the five blocks; inside this "
-                       "pool's containers the busy counters read 0 and the clock files do not follow the load: recorded for what they are worth)")
     out = dict(
         metric="HELL fp64 SpMV GFLOP/s + achieved HBM GB/s (% of roofline), 1 GPU",
         value=round(flops * args.steps * world / wall * 1e-9, 2), unit="GFLOP/s", n_gpus=world,
@@ -784,15 +808,28 @@ def run_spmv(args, rank, world):
                               "spgpuGetLastSpmvForm reports: sweep" if headline_form == "sweep" else
                               "slabSpmvKernel<double, RPL 2, 1 phase, HELL, nt, 8 columns/stage, prefetch after gathers, tail> in the form "
                               f"spgpuGetLastSpmvForm reports: {headline_form}"), algorithmic_bytes_per_launch=alg,
-                      kernel_ms=round(per_launch * 1e3, 5), kernel_ms_blocks=spread(blocks)),
-        device=device,
+                      kernel_ms=round(per_launch * 1e3, 5)),
     )
+    if args.full:
+        # the same launches once more in five blocks, with what the card reports about itself sampled beside them: a memory-bound
+        # kernel runs at speeds several per cent apart from card to card and from one set of allocations to the next
+        #  -- the record says which card, in which state, and how much the blocks differ
+        from spgpu_amd import gpu_state
+        card = gpu_state.Card(torch.cuda.current_device())
+        with gpu_state.Sampler(card) as sampler:
+            blocks = [time_launches(stream, step, max(args.steps // 5, 10)) / max(args.steps // 5, 10) * 1e3 for _ in range(5)]
+        out["roofline"]["kernel_ms_blocks"] = spread(blocks)
+        out["device"] = dict(card.identity(), name=torch.cuda.get_device_name(dev), during_timed_blocks=sampler.summary(),
+                             note="sysfs of the card as this process sees it (clocks / power sampled every 4 ms during the five blocks; inside "
+                                  "a container the busy counters may read 0 and the clock files may not follow the load: recorded for what "
+                                  "they are worth)")
 
     if rank == 0:
-        step()
-        torch.cuda.synchronize()
-        out["parity"] = spot_check_hell(h, x, y, z, 1.0, 0.0)
-        if not args.no_extras:
+        if args.full:
+            step()
+            torch.cuda.synchronize()
+            out["parity"] = spot_check_hell(h, x, y, z, 1.0, 0.0)
+        if args.full and not args.no_extras:
             extras = {}
             # beta != 0 on the headline matrix
             s2 = launcher(h, x, y, z, 1.0, 0.5)
@@ -979,7 +1016,7 @@ def run_spmv(args, rank, world):
                                                              live_attempt=detail)
             if world == 1:
                 # the N = 1 point of the curve `--gpus N` (N > 1) measures: same sharded SpMM step on one rank
-                one = measure_spmm(args, 0, 1, handle, stream, dev, 50, 5)
+                one = measure_spmm(args, 0, 1, handle, stream, dev, 50, 5, full=True)
                 out["spmm_1gpu"] = dict(value=one["value"], unit=one["unit"], ms_per_step=one["ms_per_step"],
                                         workload=one["config"]["workload"], roofline_frac=one["roofline"]["frac"],
                                         kernel_ms=one["roofline"]["kernel_ms"], parity=one["parity"])
@@ -1003,15 +1040,16 @@ def run_spmm(args, rank, world):
     handle = capi.create_handle(torch.cuda.current_device())
     stream = torch.cuda.Stream()
     capi.spgpuSetStream(handle, C.c_void_p(stream.cuda_stream))
-    out = measure_spmm(args, rank, world, handle, stream, dev, args.steps, args.warmup)
+    out = measure_spmm(args, rank, world, handle, stream, dev, args.steps, args.warmup, full=args.full, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     capi.spgpuDestroy(handle)
 
 
-def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
+def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup, full=False, dump=None):
     """The sharded SpMM step on `world` ranks (world == 1: the single-GPU point of the same curve).  Returns the
-    JSON record on rank 0, None elsewhere."""
+    JSON record on rank 0, None elsewhere.  full: also the untimed products / exchanges alone and the oracle check on
+    every rank; dump: a directory for rank 0's Z of the last timed step (dump_outputs)."""
     import torch
     from spgpu_amd import capi, sharded, synth
 
@@ -1197,8 +1235,10 @@ def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if dump and rank == 0:
+        dump_outputs(dump, dict(z=z_local))     # rank 0's rows of Z, last timed step
 
-    # untimed: the local products alone (on whatever the exchange buffer holds) and the exchanges alone
+    # untimed (full only): the local products alone (on whatever the exchange buffer holds) and the exchanges alone
     def timed(fn, reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(stream):
@@ -1211,12 +1251,12 @@ def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
         torch.cuda.synchronize()
         return a.elapsed_time(b) / reps * 1e-3
 
-    t_compute = sorted(timed(products_only, 10) for _ in range(3))[1]   # median of three blocks of 10
-    t_gather = timed(gather_only, 10) if distributed and (split or world > 1) else 0.0
-    t_needed = timed(needed_only, 10) if both and distributed else 0.0
+    t_compute = sorted(timed(products_only, 10) for _ in range(3))[1] if full else 0.0   # median of three blocks of 10
+    t_gather = timed(gather_only, 10) if full and distributed and (split or world > 1) else 0.0
+    t_needed = timed(needed_only, 10) if full and both and distributed else 0.0
     # the other exchange's step, measured in the same process (same products; what differs is what moves)
     t_step_other = 0.0
-    if both and distributed:
+    if full and both and distributed:
         t_step_other = timed(step_allgather if needed_mode else step_needed, max(3, steps // 10))
         if world > 1:
             torch.cuda.synchronize()
@@ -1225,10 +1265,11 @@ def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
             t_step_other = float(t.item())
     t_step_allgather = t_step_other if needed_mode else 0.0
     # the step under test last, for the parity check below
-    with torch.cuda.stream(stream):
-        step()
+    if full:
+        with torch.cuda.stream(stream):
+            step()
     torch.cuda.synchronize()
-    received = rows_received() if both else None
+    received = rows_received() if full and both else None
     for plan in plans.values():
         capi.spgpuDhellspmmShardedDestroy(plan)
     if comm is not None:
@@ -1242,35 +1283,37 @@ def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
     # every rank regenerated from the ranks' seeds -- the first rows of a rank's block name columns of its neighbour's block, so a
     # rank whose exchange delivered the wrong rows (or none) fails here.  The first real RCCL run of this code is the driver's
     # scale run: the line says how many ranks were seen and how many of them checked out.
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import numpy as np
-    import oracle_api as O
-    whole = synth.hell_uniform_on_device(rows_local, L, args.spmm_pattern, "D", 32, seed=11 + rank, device=dev,
-                                         n_cols=n_total, row_offset=first) if split else own
-    x_everywhere = torch.cat([synth.device_vector(rows_local * k, "D", 21 + r, dev).view(rows_local, k) for r in range(world)])
-    torch.cuda.synchronize()
-    sub = synth.hell_rows_to_host(whole, 0, 1024)
-    want = O.hell_spmm(sub, x_everywhere.cpu().numpy(), None, 1.0, 0.0)
-    del x_everywhere
-    got = z_local[:1024].cpu().numpy()
-    if split:
-        mine_ok = bool(np.max(np.abs(got - want) / (np.abs(want) + 1.0)) <= 1e-12)
-        parity = "within 1e-12 of oracle on 1024 rows (own+rest regroup the sums)" if mine_ok else "MISMATCH"
-    else:
-        mine_ok = got.tobytes() == want.tobytes()
-        parity = "bit-exact vs oracle on 1024 rows" if mine_ok else "MISMATCH"
-    ranks_seen, ranks_ok = 1, int(mine_ok)
-    if world > 1:
-        # one small all-gather of (rank, did my window check out) over the same backend as the run: who is there, who agrees
-        mine = torch.tensor([float(rank), 1.0 if mine_ok else 0.0], device=dev, dtype=torch.float64)
-        everyone_said = torch.zeros(2 * world, device=dev, dtype=torch.float64)
-        dist.all_gather_into_tensor(everyone_said, mine)
+    parity, ranks_seen, ranks_ok = None, None, None
+    if full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import numpy as np
+        import oracle_api as O
+        whole = synth.hell_uniform_on_device(rows_local, L, args.spmm_pattern, "D", 32, seed=11 + rank, device=dev,
+                                             n_cols=n_total, row_offset=first) if split else own
+        x_everywhere = torch.cat([synth.device_vector(rows_local * k, "D", 21 + r, dev).view(rows_local, k) for r in range(world)])
         torch.cuda.synchronize()
-        said = everyone_said.cpu().numpy().reshape(world, 2)
-        ranks_seen = int(np.unique(said[:, 0]).size)
-        ranks_ok = int(said[:, 1].sum())
-        if ranks_ok != world:
-            parity += f"; {world - ranks_ok} of {world} ranks MISMATCH"
+        sub = synth.hell_rows_to_host(whole, 0, 1024)
+        want = O.hell_spmm(sub, x_everywhere.cpu().numpy(), None, 1.0, 0.0)
+        del x_everywhere
+        got = z_local[:1024].cpu().numpy()
+        if split:
+            mine_ok = bool(np.max(np.abs(got - want) / (np.abs(want) + 1.0)) <= 1e-12)
+            parity = "within 1e-12 of oracle on 1024 rows (own+rest regroup the sums)" if mine_ok else "MISMATCH"
+        else:
+            mine_ok = got.tobytes() == want.tobytes()
+            parity = "bit-exact vs oracle on 1024 rows" if mine_ok else "MISMATCH"
+        ranks_seen, ranks_ok = 1, int(mine_ok)
+        if world > 1:
+            # one small all-gather of (rank, did my window check out) over the same backend as the run: who is there, who agrees
+            mine = torch.tensor([float(rank), 1.0 if mine_ok else 0.0], device=dev, dtype=torch.float64)
+            everyone_said = torch.zeros(2 * world, device=dev, dtype=torch.float64)
+            dist.all_gather_into_tensor(everyone_said, mine)
+            torch.cuda.synchronize()
+            said = everyone_said.cpu().numpy().reshape(world, 2)
+            ranks_seen = int(np.unique(said[:, 0]).size)
+            ranks_ok = int(said[:, 1].sum())
+            if ranks_ok != world:
+                parity += f"; {world - ranks_ok} of {world} ranks MISMATCH"
 
     if rank == 0:
         out = dict(
@@ -1287,23 +1330,26 @@ def measure_spmm(args, rank, world, handle, stream, dev, steps, warmup):
                         rows_per_gpu=rows_local, rows_total=n_total, rhs=k, pattern=args.spmm_pattern,
                         exchange="needed rows (all_to_all)" if needed_mode else "all-gather",
                         parallelism=f"row partition x{world}, " + ("needed-rows exchange" if needed_mode else "all-gather of X")
-                                    + (", own/rest column split (overlap)" if split else "")),
-            roofline=dict(bound="hbm", achieved=round(alg / t_compute * 1e-9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                          frac=round(alg / t_compute * 1e-9 / HBM_PEAK_GBS, 4),
-                          traffic=None if split else committed_traffic(rows_local, L, args.spmm_pattern, rhs=k),
-                          kernel="hellSpmmStripKernel<double, 2, 2>",
-                          algorithmic_bytes_per_launch=alg, kernel_ms=round(t_compute * 1e3, 4)),
-            spmm=dict(compute_only_ms=round(t_compute * 1e3, 4), allgather_only_ms=round(t_gather * 1e3, 4),
-                      compute_only_gflops_total=round(flops_total / t_compute * 1e-9, 1),
-                      allgather_GBps_per_rank=round((world - 1) * rows_local * k * 8 / t_gather * 1e-9, 1) if t_gather else None,
-                      needed_rows_only_ms=round(t_needed * 1e3, 4) if both and t_needed else None,
-                      needed_rows_received_per_rank=received, driver=driver,
-                      rccl_ranks_seen=ranks_seen, ranks_whose_window_matches_the_oracle=ranks_ok,
-                      exchange_bytes_per_rank=dict(allgather=(world - 1) * rows_local * k * 8,
-                                                   needed_rows=(received * k * 8 if received is not None else None)),
-                      allgather_step_ms=round(t_step_allgather * 1e3, 4) if t_step_allgather else None,
-                      allgather_step_gflops_total=round(flops_total / t_step_allgather * 1e-9, 1) if t_step_allgather else None),
-            parity=parity, cpu_baseline=None)
+                                    + (", own/rest column split (overlap)" if split else "")))
+        if full:
+            out.update(
+                roofline=dict(bound="hbm", achieved=round(alg / t_compute * 1e-9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                              frac=round(alg / t_compute * 1e-9 / HBM_PEAK_GBS, 4),
+                              traffic=None if split else committed_traffic(rows_local, L, args.spmm_pattern, rhs=k),
+                              kernel="hellSpmmStripKernel<double, 2, 2>",
+                              algorithmic_bytes_per_launch=alg, kernel_ms=round(t_compute * 1e3, 4)),
+                spmm=dict(compute_only_ms=round(t_compute * 1e3, 4), allgather_only_ms=round(t_gather * 1e3, 4),
+                          compute_only_gflops_total=round(flops_total / t_compute * 1e-9, 1),
+                          allgather_GBps_per_rank=round((world - 1) * rows_local * k * 8 / t_gather * 1e-9, 1) if t_gather else None,
+                          needed_rows_only_ms=round(t_needed * 1e3, 4) if both and t_needed else None,
+                          needed_rows_received_per_rank=received, driver=driver,
+                          rccl_ranks_seen=ranks_seen, ranks_whose_window_matches_the_oracle=ranks_ok,
+                          exchange_bytes_per_rank=dict(allgather=(world - 1) * rows_local * k * 8,
+                                                       needed_rows=(received * k * 8 if received is not None else None)),
+                          allgather_step_ms=round(t_step_allgather * 1e3, 4) if t_step_allgather else None,
+                          allgather_step_gflops_total=round(flops_total / t_step_allgather * 1e-9, 1) if t_step_allgather else None),
+                parity=parity)
+        out["cpu_baseline"] = None
         if world > 1:
             out["scaling_base"] = ("this line is the row-sharded SpMM of BASELINE configs[4]; its N = 1 point is `spmm_1gpu.value` of the "
                                    "`--gpus 1` line (same 5 M rows x 32 x 16 rhs per GPU, no exchange), NOT that line's `value`, which is the "
@@ -1405,6 +1451,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     rank = int(os.environ.get("RANK", 0))

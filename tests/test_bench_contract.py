@@ -65,3 +65,41 @@ def test_gpus_flag_is_honoured_or_refused(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "4", "--steps", "3"] and cmd[-5].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: an output of at most DUMP_VALUES values is written whole; a larger one as the same fixed rows every time
+    (distinct, ascending), with their numbers beside it -- float64 stays float64, rows keep their width."""
+    import numpy as np
+    import torch
+    small = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), dict(z=small))
+    assert sorted(os.listdir(tmp_path / "a")) == ["z.npy"]
+    got = np.load(tmp_path / "a" / "z.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy())
+
+    rows, k = 3 * bench.DUMP_VALUES // 16 + 7, 16
+    wide = torch.arange(rows * k, dtype=torch.float64).view(rows, k)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), dict(z=wide))
+    picked = np.load(tmp_path / "b" / "z_rows.npy")
+    assert picked.dtype == np.float64 and picked.size == bench.DUMP_VALUES // k
+    assert np.all(np.diff(picked) > 0) and picked[0] >= 0 and picked[-1] < rows
+    got = np.load(tmp_path / "b" / "z.npy")
+    assert got.shape == (picked.size, k) and np.array_equal(got, wide.numpy()[picked.astype(np.int64)])
+    for name in ("z.npy", "z_rows.npy"):
+        assert (tmp_path / "b" / name).read_bytes() == (tmp_path / "c" / name).read_bytes()
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64 << 20
+
+
+def test_plain_run_options():
+    """A plain run is the timed steps only (--full off by default), and --steps has to be a real number of steps."""
+    import subprocess
+    import unittest.mock
+    with unittest.mock.patch.object(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]):
+        args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *bad], capture_output=True, text=True,
+                             timeout=120)
+        assert run.returncode != 0 and "--steps must be >= 1" in run.stderr

@@ -19,7 +19,7 @@ def test_two_ranks_on_one_gpu(gpu, exchange, pattern):
     port = 29600 + os.getpid() % 300 + (1 if exchange == "needed" else 0)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--spmm-rows-per-gpu", "200000", "--spmm-pattern", pattern, "--exchange", exchange]
+           "--spmm-rows-per-gpu", "200000", "--spmm-pattern", pattern, "--exchange", exchange, "--full"]
     run = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -46,7 +46,7 @@ def test_gpus_two_direct_form(gpu):
     for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(name, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--spmm-rows-per-gpu", "100000"]
+           "--spmm-rows-per-gpu", "100000", "--full"]
     run = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]

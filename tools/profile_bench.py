@@ -4,7 +4,7 @@
 
     python tools/profile_bench.py <tag> spmv|spmv_frozen|spmm
 
-  1. rocprofv3 --kernel-trace --stats -- python3 bench.py ... --no-extras      -> <tag>_bench_<kind>_kernel_stats.csv
+  1. rocprofv3 --kernel-trace --stats -- python3 bench.py ... --full --no-extras -> <tag>_bench_<kind>_kernel_stats.csv
   2. rocprofv3 --pmc FETCH_SIZE ... and --pmc WRITE_SIZE ... (separate passes)  -> <tag>_bench_<kind>_pmc.json
 The program after `--` is python3 itself (no env / shell hop: the profiler's preloaded library initialises the GPU)."""
 import csv
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, kind = sys.argv[1], sys.argv[2]
 out = os.path.join(ROOT, "gpurun_out", f"profile_{tag}")
 os.makedirs(out, exist_ok=True)
-bench = [os.path.join(ROOT, "bench.py"), "--no-extras"] + (["--workload", "spmm"] if kind == "spmm" else []) + (["--frozen"] if kind == "spmv_frozen" else [])
+bench = [os.path.join(ROOT, "bench.py"), "--full", "--no-extras"] + (["--workload", "spmm"] if kind == "spmm" else []) + (["--frozen"] if kind == "spmv_frozen" else [])
 # spmv_frozen: the headline matrix after spgpuHellSpmvFreeze (bench.py --frozen): the PACKED instantiation of the same kernel
 kernel_key = ("hellSpmmStripKernel" if kind == "spmm" else
               "slabSpmvKernel<double, 2, 1, true, true, 8, 2, true, 0, true, 256, 0, false, 1, 0, true>" if kind == "spmv_frozen" else
@@ -58,7 +58,7 @@ read_bytes, write_bytes = 2 * fetch * 1024, write * 1024
 summary = dict(
     workload=dict(rows=rec["config"].get("rows", rec["config"].get("rows_per_gpu")), nnz_per_row=32, pattern=rec["config"]["pattern"],
                   **({"rhs": rec["config"]["rhs"]} if kind == "spmm" else {})),
-    command="rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 100 --warmup 10 --no-extras"
+    command="rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 100 --warmup 10 --full --no-extras"
             + (" --workload spmm" if kind == "spmm" else "") + (" --frozen" if kind == "spmv_frozen" else "")
             + " ; counters in separate runs: --pmc FETCH_SIZE --kernel-trace, --pmc WRITE_SIZE --kernel-trace (--steps 10 --warmup 2)",
     kernel=k["Name"], calls=int(k["Calls"]), average_ns=float(k["AverageNs"]), min_ns=int(k["MinNs"]), max_ns=int(k["MaxNs"]),
