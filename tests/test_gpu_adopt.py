@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_ref as X
 import oracle_api as O
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,9 @@ def test_adopted_call_equals_the_ordered_call_and_oracle(gpu, letter, pattern, n
     # and within the north_star tolerance of the plain call (another order of additions)
     scale = np.abs(alpha) * np.abs(want_plain - beta * y) + np.abs(beta * y) + np.finfo(np.float64).tiny
     assert np.max(np.abs(got - want_plain) / (TOL[letter] * (scale + np.max(np.abs(want_plain))))) <= 1.0
+    # and row by row within the bound of the extended-precision product (not a margin taken from the largest row)
+    exact, exact_scale = X.spmv(n, *X.hell_coo(_host(plain, letter, n, hack)), x, y, alpha, beta, base=0)
+    X.assert_within(got, exact, exact_scale, letter, ("adopted", letter, pattern, hack))
     # in place, beta = 0
     want0 = O.spmv_tail(_host(ordered, letter, n, hack), x, None, 1.25, 0.0, r_idx=ordered["rIdx"].cpu().numpy(), **O.slab_shape(letter, "ragged", deep_cap=O.DEEP_CAP))
     dz.fill_(float("nan"))

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_ref as X
 import oracle_api as O
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,8 @@ def test_frozen_call_equals_unfrozen_call_and_oracle(gpu, letter, window, long_r
         torch.cuda.synchronize()
         assert dz.cpu().numpy().tobytes() == want.tobytes()
     assert capi.plan_counts(gpu)[0] - uses0 == 3                    # every frozen call ran from the plan
+    exact, scale = X.spmv(n, *X.hell_coo(sub), x, y, -0.5, 2.0, r_idx=r_idx, base=sub["base"])
+    X.assert_within(dz.cpu().numpy(), exact, scale, letter, ("frozen", letter, window, long_rows, aligned, hack, pattern, near))
     # in place (z = y), beta = 0
     want0 = O.spmv_tail(sub, x, None, 1.25, 0.0, r_idx=r_idx, **O.slab_shape(letter, "ragged", deep_cap=O.DEEP_CAP))
     dz.fill_(float("nan"))
@@ -262,12 +265,15 @@ def test_frozen_matrix_without_row_order_same_bits(gpu, letter, kind):
         span = np.repeat(np.maximum(lengths * 3, 64), lengths)
         cols = (rows - span // 2 + (k * span) // np.repeat(lengths, lengths)) % n       # ascending inside a row, within +-span/2
         if kind == "far_escapes":
+            # x is 70 000 + n long and the far columns lie 70 000 beyond the near ones: 16 bits cannot reach them from any group
             far = rng.random(rows.size) < 0.005
-            cols = np.where(far, (cols + n // 2 + 70000) % n, cols)
+            cols = np.where(far, cols + 70000, cols)
+            entries, escapes = X.unordered_escapes(n, rows, cols, letter)
+            assert 0 < escapes and X.freeze_keeps(entries, escapes), (entries, escapes)
         coo = (n, n, rows.astype(np.int32), cols.astype(np.int32), synth.values_for(letter, 5, rows.size))
     ell, hell = _hell_of(coo, letter, base=base)
     dev = formats.DeviceHell(hell)
-    x, y = synth.values_for(letter, 31, n), synth.values_for(letter, 32, n)
+    x, y = synth.values_for(letter, 31, n + (70000 if kind == "far_escapes" else 0)), synth.values_for(letter, 32, n)
     want = O.default_spmv(hell, x, y, 1.5, -0.25)
     for _ in range(3):
         assert _spmv(gpu, dev, x, y, 1.5, -0.25).tobytes() == want.tobytes()
@@ -280,6 +286,8 @@ def test_frozen_matrix_without_row_order_same_bits(gpu, letter, kind):
     # every call found the frozen record -- unless AUTO has settled on the LDS-tile form for this matrix (columns inside a window
     # an LDS tile holds, rows longer than a stage): that form has no packed variant and runs as before
     assert used == 4 if kind.startswith("band") else used in (0, 4), used
+    exact, scale = X.spmv(n, *X.hell_coo(hell), x, y, 1.5, -0.25, base=base)
+    X.assert_within(_spmv(gpu, dev, x, y, 1.5, -0.25), exact, scale, letter, ("frozen, no row order", letter, kind))
     want0 = O.default_spmv(hell, x, None, 2.0, 0.0)
     assert _spmv(gpu, dev, x, None, 2.0, 0.0).tobytes() == want0.tobytes()
     assert capi.spgpuSpmvThaw(gpu, _dp(dev.rP)) == capi.SPGPU_SUCCESS
@@ -301,11 +309,13 @@ def test_frozen_gather_form_without_row_order(gpu, letter):
     k = np.arange(rows.size, dtype=np.int64) - np.repeat(np.cumsum(lengths) - lengths, lengths)
     span = np.repeat(np.maximum(lengths * 4, 64), lengths)
     cols = (rows - span // 2 + (k * span) // np.repeat(lengths, lengths)) % n
-    cols = np.where(rng.random(rows.size) < 0.004, (cols + 90000) % n, cols)
+    cols = np.where(rng.random(rows.size) < 0.004, cols + 90000, cols)      # x is 90 000 + n long: escapes from every group
+    entries, escapes = X.unordered_escapes(n, rows, cols, letter)
+    assert 0 < escapes and X.freeze_keeps(entries, escapes), (entries, escapes)
     coo = (n, n, rows.astype(np.int32), cols.astype(np.int32), synth.values_for(letter, 5, rows.size))
     ell, hell = _hell_of(coo, letter)
     dev = formats.DeviceHell(hell)
-    x = synth.values_for(letter, 7, n)
+    x = synth.values_for(letter, 7, n + 90000)
     want = O.default_spmv(hell, x, None, 1.0, 0.0)
     capi.spgpuSetSpmvForm(gpu, capi.FORM_GATHER)
     try:

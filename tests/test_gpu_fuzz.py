@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_ref as X
 import oracle_api as O
 
 pytestmark = pytest.mark.gpu
@@ -64,17 +65,18 @@ def _vector(rng, letter, n):
     return v
 
 
-def _exact(case, x, y, alpha, beta):
-    cplx = case["letter"] in "CZ"
-    wide = np.clongdouble if cplx else np.longdouble
-    prod = case["vals"].astype(wide) * x.astype(wide)[case["cols"]]
-    acc = np.zeros(case["n"], wide)
-    np.add.at(acc, case["rows"], prod)
-    mag = np.zeros(case["n"], np.longdouble)
-    np.add.at(mag, case["rows"], np.abs(prod))
-    z = wide(alpha) * acc + (wide(beta) * y.astype(wide) if beta != 0 else 0)
-    scale = abs(alpha) * mag + (np.abs(wide(beta) * y.astype(wide)) if beta != 0 else 0)
-    return z, scale.astype(np.float64)
+def _exact(case, x, y, alpha, beta, r_idx=None):
+    return X.spmv(case["n"], case["rows"], case["cols"], case["vals"], x, y if beta != 0 else None, alpha, beta, r_idx=r_idx)
+
+
+def _complex_scalars(seed, letter, alpha, beta):
+    """C and Z: imaginary parts for alpha and beta (beta = 0 stays 0), from a generator of their own -- the matrices, orders and
+    forms each seed draws do not change."""
+    if letter not in "CZ":
+        return alpha, beta
+    g = np.random.default_rng([seed, 0xC0DE])
+    im = [-1.0, -0.25, 0.5, 2.0]
+    return complex(alpha, im[int(g.integers(0, 4))]), (complex(beta, im[int(g.integers(0, 4))]) if beta != 0 else beta)
 
 
 @pytest.mark.parametrize("seed", range(72))
@@ -102,19 +104,9 @@ def test_random_case_within_the_bound(gpu, seed):
     alpha = [1.0, -0.75, 2.5][int(rng.integers(0, 3))]
     beta = [0.0, 1.0, -0.5][int(rng.integers(0, 3))]
     in_place = beta != 0 and bool(rng.integers(0, 2))
-    # what the product must be, in terms of the ORIGINAL rows
-    if order == "permutation":
-        z_rows, scale_rows = _exact(case, x, np.zeros(n, y.dtype), alpha, 0.0)        # row sums first, then through rIdx
-        want = np.zeros(n, z_rows.dtype)
-        want[r_idx] = z_rows
-        scale = np.zeros(n)
-        scale[r_idx] = scale_rows
-        if beta != 0:
-            wide = want.dtype.type
-            want = want + wide(beta) * y.astype(want.dtype)
-            scale = scale + np.abs(wide(beta) * y.astype(want.dtype)).astype(np.float64)
-    else:
-        want, scale = _exact(case, x, y, alpha, beta)
+    alpha, beta = _complex_scalars(seed, letter, alpha, beta)
+    # what the product must be, in terms of the ORIGINAL rows: row sums through rIdx for a permutation, y read at z's row
+    want, scale = _exact(case, x, y, alpha, beta, r_idx=r_idx if order == "permutation" else None)
     dx, dy = formats.to_device(x), formats.to_device(y)
     rI = formats.to_device(r_idx)
     for form in (capi.FORM_AUTO, capi.FORM_GATHER, capi.FORM_STRIPS, capi.FORM_XTILE, capi.FORM_SWEEP):
@@ -138,12 +130,8 @@ def test_random_case_within_the_bound(gpu, seed):
                         capi.ellspmv[letter](gpu, _p(dz), _p(yy), capi.scalar(letter, alpha), _p(cM), _p(rP), ell["pitch"], ell["pitch"],
                                              _p(rS), _p(rI), 8, ell["max_row"], n, _p(dx), capi.scalar(letter, beta), base)
                     torch.cuda.synchronize()
-                    got = dz.cpu().numpy()
-                    err = np.abs(got.astype(want.dtype) - want).astype(np.float64)
-                    bound = TOL[letter] * scale + 1e-300
-                    worst = int(np.argmax(err - bound))
-                    assert np.all(err <= bound), (seed, letter, case["kind"], case["pattern"], str(order), fmt, form, repeat, n, hack,
-                                                  base, worst, got[worst], want[worst])
+                    X.assert_within(dz.cpu().numpy(), want, scale, letter, (seed, letter, case["kind"], case["pattern"], str(order), fmt,
+                                                                            form, repeat, n, hack, base, alpha, beta))
         finally:
             capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
 
@@ -182,8 +170,8 @@ def test_random_diagonal_case_within_the_bound(gpu, seed):
     x, y = _vector(rng, letter, cols_n), _vector(rng, letter, n)
     alpha = [1.0, -0.75, 2.5][int(rng.integers(0, 3))]
     beta = [0.0, 1.0, -0.5][int(rng.integers(0, 3))]
+    alpha, beta = _complex_scalars(seed, letter, alpha, beta)
     want, scale = _exact(case, x, y, alpha, beta)
-    bound = TOL[letter] * scale + 1e-300
     dx, dy = formats.to_device(x), formats.to_device(y)
     dia = formats.coo_to_dia(n, cols_n, rows, cols, vals)
     mats = [("hdia from coo", formats.DeviceHdia(formats.coo_to_hdia(n, cols_n, rows, cols, vals, hack))),
@@ -194,7 +182,4 @@ def test_random_diagonal_case_within_the_bound(gpu, seed):
             dz = dy.clone() if in_place else torch.full((n,), float("nan"), dtype=dx.dtype, device="cuda")
             mat.spmv(gpu, dz, dz if in_place else (dy if beta != 0 else None), alpha, dx, beta)
             torch.cuda.synchronize()
-            got = dz.cpu().numpy()
-            err = np.abs(got.astype(want.dtype) - want).astype(np.float64)
-            worst = int(np.argmax(err - bound))
-            assert np.all(err <= bound), (seed, letter, name, n, cols_n, hack, offsets.tolist(), worst, got[worst], want[worst])
+            X.assert_within(dz.cpu().numpy(), want, scale, letter, (seed, letter, name, n, cols_n, hack, offsets.tolist(), alpha, beta))

@@ -174,3 +174,75 @@ def test_spmm_never_uses_padding(gpu, letter, pattern, count):
         want = O.hell_spmm(host, X, Y if beta != 0 else None, 1.25, beta)
         assert not np.isnan(want).any()
         assert dZ.cpu().numpy().tobytes() == want.tobytes(), beta
+
+
+@pytest.mark.parametrize("letter", ["S", "D", "C"])
+@pytest.mark.parametrize("path", ["frozen unordered", "frozen ordered", "adopted hell", "adopted ell"])
+def test_frozen_and_adopted_paths_never_use_padding(gpu, tuning, letter, path):
+    """The opt-in paths of include/spgpu/tuning.h on matrices whose padding slots hold NaN and random columns, with the library's
+    uninitialised scratch poisoned (SPGPU_POISON_SCRATCH=1, set before Freeze / Adopt: the packed words, the adopted copy's padding):
+    the oracle's bytes, as the paths they stand for."""
+    import torch
+    from spgpu_amd import capi, formats, synth
+    n, hack = 5 * 2048 + 77, 32
+    tuning(SPGPU_POISON_SCRATCH=1)
+    code = capi.TYPE_CODE[letter]
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    real = {"S": "S", "D": "D", "C": "S"}[letter]
+    lengths = np.minimum(synth.power_law_lengths(n, 10.0, 400, 5), 400)
+    coo = synth.ragged_coo_on_device(lengths, n, "near", 300, real, seed=19)
+    if letter == "C":
+        coo = (coo[0], coo[1], torch.complex(coo[2], torch.flip(coo[2], [0])))
+    x, y = synth.values_for(letter, 71, n), synth.values_for(letter, 72, n)
+    dx, dy = formats.to_device(x), formats.to_device(y)
+    if path == "frozen ordered":
+        h = _matrix(gpu, n, letter, 2048, 60, True, hack=hack, longest=900, near=500, seed=78)
+    elif path == "adopted ell":
+        rows_h, cols_h, vals_h = (t.cpu().numpy() for t in coo)
+        ell = formats.coo_to_ell(n, rows_h, cols_h, vals_h)
+        cM, rP, rS = formats.to_device(ell["values"]), formats.to_device(ell["indices"]), formats.to_device(ell["row_lengths"])
+        pad = np.arange(ell["max_row"])[:, None] >= ell["row_lengths"][None, :]      # [k, r]: slot k * pitch + r
+        mask = np.zeros(ell["values"].size, bool)
+        mask.reshape(ell["max_row"], ell["pitch"])[:, :n] = pad
+        mask.reshape(ell["max_row"], ell["pitch"])[:, n:] = True
+        padding = torch.from_numpy(mask).cuda()
+        cM[padding] = float("nan")
+        rP[padding] = torch.randint(0, n, (int(mask.sum()),), device="cuda", dtype=torch.int32)
+        torch.cuda.synchronize()
+        h = dict(cM=cM, rP=rP, rS=rS, rIdx=None, hack_offsets=None)
+    else:
+        h = formats.coo_to_ordered_hell_device(gpu, n, *coo, letter, hack, 0, 0, order=False)
+    if path != "adopted ell":
+        lens = h["rS"][:n].cpu().numpy().astype(np.int64)
+        offsets = h["hack_offsets"].cpu().numpy().astype(np.int64)
+        assert _poison_hell(h["cM"][:h["slots"]], h["rP"][:h["slots"]], lens, offsets, hack, n) > 0
+    if path.startswith("adopted"):
+        ordered = formats.coo_to_ordered_hell_device(gpu, n, *coo, letter, 32, 2048, 256, aligned=True)
+        want = O.spmv_tail(_host(ordered, letter, n), x, y, -0.5, 2.0, r_idx=ordered["rIdx"].cpu().numpy(),
+                           **O.slab_shape(letter, "ragged", deep_cap=O.DEEP_CAP))
+    elif path == "frozen ordered":
+        want = O.spmv_tail(_host(h, letter, n, hack), x, y, -0.5, 2.0, r_idx=h["rIdx"].cpu().numpy(), **O.slab_shape(letter, "ragged", deep_cap=O.DEEP_CAP))
+    else:
+        want = O.default_spmv(_host(h, letter, n, hack), x, y, -0.5, 2.0)
+    assert not np.isnan(want.view(np.float32 if letter in "SC" else np.float64)).any()
+    if path == "adopted ell":
+        said = capi.spgpuEllSpmvAdopt(gpu, code, p(h["cM"]), p(h["rP"]), ell["pitch"], ell["pitch"], p(h["rS"]), ell["max_row"], n, 0)
+    elif path == "adopted hell":
+        said = capi.spgpuHellSpmvAdopt(gpu, code, p(h["cM"]), p(h["rP"]), hack, p(h["hack_offsets"]), p(h["rS"]), n, 0)
+    else:
+        said = capi.spgpuHellSpmvFreeze(gpu, code, p(h["cM"]), p(h["rP"]), hack, p(h["hack_offsets"]), p(h["rS"]), p(h["rIdx"]), n, 0)
+    try:
+        assert said == capi.SPGPU_SUCCESS
+        for call in range(3):
+            dz = torch.full((n,), float("nan"), dtype=dx.dtype, device="cuda")
+            torch.cuda.synchronize()
+            if path == "adopted ell":
+                capi.ellspmv[letter](gpu, p(dz), p(dy), capi.scalar(letter, -0.5), p(h["cM"]), p(h["rP"]), ell["pitch"], ell["pitch"], p(h["rS"]),
+                                     None, 10, ell["max_row"], n, p(dx), capi.scalar(letter, 2.0), 0)
+            else:
+                _call(gpu, letter, h, n, dz, dy, dx, -0.5, 2.0, hack)
+            torch.cuda.synchronize()
+            assert dz.cpu().numpy().tobytes() == want.tobytes(), (path, call)
+    finally:
+        capi.spgpuSpmvThaw(gpu, p(h["rP"]))
+    assert capi.spgpuSpmvFrozenBytes(gpu) == 0

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_ref as X
 import oracle_api as O
 
 pytestmark = pytest.mark.gpu
@@ -69,6 +70,9 @@ def test_spmm_leading_dimensions_row_reorder_and_in_place(gpu):
     want = O.hell_spmm(hell, np.ascontiguousarray(Xp[:, :count]), np.ascontiguousarray(Yp[:, :count]), 2.0, 0.75, r_idx=perm)
     assert got[:, :count].tobytes() == want.tobytes()
     assert np.array_equal(got[:, count:], Yp[:, count:])   # padding columns of Z untouched
+    r, c, v = X.hell_coo(hell)
+    exact, scale = X.spmm(rows, r, c, v, Xp, Yp, 2.0, 0.75, count, ldx=ldx, ldy=ldz, r_idx=perm, base=hell["base"])
+    X.assert_within(got[:, :count], exact, scale, "D", "leading dimensions, rIdx, in place")
 
 
 @pytest.mark.parametrize("letter", "SD")
@@ -225,6 +229,8 @@ def test_spmm_randomized_shapes(gpu):
         want = O.hell_spmm(hell, np.ascontiguousarray(Xp[:, :count]), np.ascontiguousarray(Yp[:, :count]) if beta else None, 0.5, beta)
         assert got[:, :count].tobytes() == want.tobytes(), (trial, letter, hs, base, rows, cols, count, ld, max_len, half)
         assert np.array_equal(got[:, count:], Yp[:, count:]), trial
+        exact, scale = X.spmm(rows, r, c, v, Xp, Yp if beta else None, 0.5, beta, count, ldx=ld, ldy=ld)
+        X.assert_within(got[:, :count], exact, scale, letter, (trial, letter, hs, base, rows, cols, count, ld, max_len, half))
 
 
 @pytest.mark.parametrize("hs", [8, 48, 80])
