@@ -18,7 +18,7 @@ CPP_SRCS  := $(wildcard $(CSRC)/*.cpp)
 OBJS      := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.hip.o,$(HIP_SRCS)) \
              $(patsubst $(CSRC)/%.c,$(BUILD)/%.c.o,$(C_SRCS)) \
              $(patsubst $(CSRC)/%.cpp,$(BUILD)/%.cpp.o,$(CPP_SRCS))
-HDRS      := $(wildcard include/spgpu/*.h) $(wildcard $(CSRC)/*.h)
+HDRS      := $(wildcard include/spgpu/*.h) $(wildcard include/spgpu/ext/*.h) $(wildcard $(CSRC)/*.h)
 
 .PHONY: all lib oracle ref tools clean
 all: lib oracle ref tools
@@ -46,8 +46,8 @@ $(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) -x c++ $(CFLAGS) -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -c $< -o $@
 
-# Plain-C callers of the C ABI (gcc, no hipcc): the reference's ctest.c / hellPerf.cpp / diaPerf.cpp flows and a CG solver.
-TOOLS := tools/ctest_amd.bin tools/hellperf_amd.bin tools/diaperf_amd.bin tools/cg_amd.bin
+# Plain-C callers of the C ABI (gcc, no hipcc): the reference's ctest.c / hellPerf.cpp / diaPerf.cpp flows and two CG solvers.
+TOOLS := tools/ctest_amd.bin tools/hellperf_amd.bin tools/diaperf_amd.bin tools/cg_amd.bin tools/cg_ragged_amd.bin
 tools: lib $(TOOLS)
 tools/%.bin: tools/%.c $(HDRS) $(LIBDIR)/libspgpu.so
 	gcc -O2 -std=gnu99 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude $< -L$(LIBDIR) -lspgpu -L$(ROCM)/lib -lamdhip64 -lm \

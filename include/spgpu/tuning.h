@@ -68,7 +68,8 @@ int spgpuDeepListsRecycled(spgpuHandle_t handle);
  * ONE launch with a shorter prologue: no probing of columns, no deep list, nothing behind the main kernel; the deep
  * sub-groups get workgroups of their own in the same grid.  The bits of z are the same with and without a plan, and with a
  * plan that has gone stale (another matrix at the same addresses): a plan decides who computes, never what or in which order.
- * A stale plan is noticed by the kernels and rebuilt by the next call.  Launches captured into a HIP graph never use a plan.
+ * A stale plan is noticed by the kernels and rebuilt by the next call.  Launches captured into a HIP graph never use a plan,
+ * unless held (spgpu/ext/graph.h).
  *   SPGPU_PLAN=0                 no plans
  *   SPGPU_PLAN_DEEP_PER_BLOCK    deep sub-groups per workgroup of theirs (default 8, 1 .. 8)
  *   SPGPU_PLAN_DEEP_RUNS         1 (default): such a workgroup takes a RUN of consecutive deep sub-groups of the list -- after an
@@ -117,8 +118,10 @@ int spgpuEllSpmvPrepare(spgpuHandle_t handle, spgpuType_t type, const void* cM, 
  * Breaking the promise is undefined behaviour in the usual sense: wrong results for the entries that changed, and reads of x at
  * columns the copy never named if rows grew (the library cannot see it: checking would mean reading rP, which is what the copy
  * saves; an ordered matrix whose row LENGTHS changed is noticed like any stale plan -- by the call that has already used the copy).
- * Launches captured into a HIP graph never use a frozen copy (a graph outlives a Thaw): they run as unfrozen calls.
- * A frozen plan ends with spgpuSpmvThaw(handle, rP), when it is the least recently used of 8 matrices, or with the handle.
+ * Launches captured into a HIP graph never use a frozen copy (a graph outlives a Thaw): they run as unfrozen calls, unless held
+ * (spgpu/ext/graph.h).
+ * A frozen plan ends with spgpuSpmvThaw(handle, rP), when it is the least recently used of 8 matrices, or with the handle
+ * (a held one: only with the handle, or after its last release).
  * spgpuSpmvFrozenBytes: device memory the handle's frozen plans hold.
  */
 int spgpuHellSpmvFreeze(spgpuHandle_t handle, spgpuType_t type, const void* cM, const int* rP, int hackSize, const int* hackOffsets, const int* rS,
@@ -140,7 +143,8 @@ long long spgpuSpmvFrozenBytes(spgpuHandle_t handle);
  * what the caller would get by ordering the matrix himself with the same device calls).  Cost: device memory for the ordered
  * matrix (spgpuSpmvFrozenBytes counts it) and ~17 ms once for the 10 M-row target.  SPGPU_UNSUPPORTED: hackSize not a multiple of 32, no memory, four
  * matrices adopted already -- or a matrix that stores less than 1.25 x the slots its ordered copy would (rows about equally long:
- * nothing to gain; spgpuHellSpmvFreeze is the call for such a matrix).  Launches captured into a HIP graph run on the caller's arrays.
+ * nothing to gain; spgpuHellSpmvFreeze is the call for such a matrix).  Launches captured into a HIP graph run on the caller's arrays,
+ * unless held (spgpu/ext/graph.h).
  * spgpuSpmvAdoptedUses: calls that ran on a copy.  (Adopt, Freeze and Thaw synchronise the handle's stream: not inside a capture.)
  */
 int spgpuHellSpmvAdopt(spgpuHandle_t handle, spgpuType_t type, const void* cM, const int* rP, int hackSize, const int* hackOffsets, const int* rS,

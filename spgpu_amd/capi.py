@@ -271,6 +271,12 @@ spgpuSpmvThaw = _decl("spgpuSpmvThaw", i32, [Handle, ptr])
 spgpuSpmvFrozenBytes = _decl("spgpuSpmvFrozenBytes", C.c_longlong, [Handle])
 spgpuEllSpmvPrepare = _decl("spgpuEllSpmvPrepare", i32, [Handle, i32, ptr, ptr, i32, i32, ptr, ptr, i32, i32, i32])
 
+# ---- ext/graph.h: holds that let captured graphs use a matrix' records ---------------------------------------
+SPGPU_IN_USE = 4  # spgpuSpmvThaw refused: a hold is on the matrix
+spgpuSpmvHold = _decl("spgpuSpmvHold", i32, [Handle, ptr])
+spgpuSpmvRelease = _decl("spgpuSpmvRelease", i32, [Handle, ptr])
+spgpuSpmvHolds = _decl("spgpuSpmvHolds", i32, [Handle, ptr])
+
 
 def plan_counts(handle):
     """(launches with a plan, analyses started, plans found stale) of the handle's ordered ELL/HELL SpMVs (tuning.h)."""

@@ -141,6 +141,8 @@ static int adoptMatrix(spgpuHandle_t handle, spgpuType_t type, const void* cM, c
     hipStream_t stream = handle->currentStream;
     if (spgpuAdoptedFind(handle, stream, cM, rP, rS, hackOffsets, rows, callerHackSize, baseIndex, valPitch, idxPitch))
         return SPGPU_SUCCESS; /* already adopted */
+    if (spgpuPlanTableHeld(handle))
+        return SPGPU_UNSUPPORTED; /* every plan record is held (include/spgpu/ext/graph.h): the copy could not be frozen or planned */
     const long long hacks = ((long long)rows + hackSize - 1) / hackSize;
     int previous = 0;
     (void)hipGetDevice(&previous);

@@ -6,6 +6,7 @@
  * kernels/ddot.cu:35).
  */
 #include "spgpu_internal.h"
+#include "spgpu/ext/graph.h"
 #include "spgpu/tuning.h"
 
 #include <pthread.h>
@@ -408,8 +409,9 @@ SpgpuSpmvPlan* spgpuPlanRecord(spgpuHandle_t pHandle, const SpgpuSpmvPlan* key)
             p->clock = ++h->planClock;
             return p;
         }
-        /* a record whose analysis is still in flight keeps its buffer and its pinned words until it has landed */
-        if (p->state == SPGPU_PLAN_BUILDING && !spgpuEventDone(p->built))
+        /* a record whose analysis is still in flight keeps its buffer and its pinned words until it has landed; a held record
+         * (spgpuSpmvHold) keeps them for as long as a captured graph may replay a launch that reads them */
+        if (p->holds > 0 || (p->state == SPGPU_PLAN_BUILDING && !spgpuEventDone(p->built)))
             continue;
         if (!oldest || p->rows == 0 || (oldest->rows != 0 && p->clock < oldest->clock))
             oldest = p;
@@ -430,8 +432,22 @@ SpgpuSpmvPlan* spgpuPlanRecord(spgpuHandle_t pHandle, const SpgpuSpmvPlan* key)
     oldest->uses = 0;
     oldest->deep = 0;
     oldest->blocks = 0;
+    oldest->holds = 0;
     oldest->clock = ++h->planClock;
     return oldest;
+}
+
+int spgpuPlanTableHeld(spgpuHandle_t pHandle)
+{
+    SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
+    int held = 0;
+    if (!h->plans)
+        return 0;
+    pthread_mutex_lock(&h->formLock);
+    for (int i = 0; i < SPGPU_PLANS; ++i)
+        held += h->plans[i].holds > 0;
+    pthread_mutex_unlock(&h->formLock);
+    return held == SPGPU_PLANS;
 }
 
 /* Lock held.  The record with this key, or NULL: looks, never makes room. */
@@ -467,16 +483,19 @@ const SpgpuAdopted* spgpuAdoptedFind(spgpuHandle_t pHandle, hipStream_t stream, 
     SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
     if (!h->adopted || __atomic_load_n(&h->adoptedCount, __ATOMIC_RELAXED) <= 0)
         return NULL;
+    /* a captured launch carries the copy's addresses for as long as the graph lives: only a held entry (spgpuSpmvHold), which Thaw
+     * leaves alone, is used there */
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
         (void)hipGetLastError();
-        return NULL;
+        capturing = hipStreamCaptureStatusActive;
     }
+    const int heldOnly = capturing != hipStreamCaptureStatusNone;
     const SpgpuAdopted* found = NULL;
     pthread_mutex_lock(&h->formLock);
     for (int i = 0; i < SPGPU_ADOPTED; ++i) {
         const SpgpuAdopted* e = &h->adopted[i];
-        if (e->rows > 0 && e->rP == (const void*)rP && e->cM == cM && e->rS == (const void*)rS && e->hackOffsets == (const void*)hackOffsets &&
+        if (e->rows > 0 && (!heldOnly || e->holds > 0) && e->rP == (const void*)rP && e->cM == cM && e->rS == (const void*)rS && e->hackOffsets == (const void*)hackOffsets &&
             e->rows == rows && e->hackSize == hackSize && e->baseIndex == baseIndex && e->valPitch == valPitch && e->idxPitch == idxPitch) {
             found = e;
             h->adoptedUses += 1;
@@ -544,12 +563,101 @@ static void freeAdopted(const SpgpuAdopted* e)
     hipFree(e->order);
 }
 
+/* Holds on the records of the matrix with this index array (include/spgpu/ext/graph.h): its plans, its adopted entry and the plans of
+ * that entry's ordered copy (keyed by the copy's indices).  delta 0: the largest count among them; +1: every READY one gains a hold
+ * (none if there is no such record and no adopted entry); -1: every held one loses one.  Returns the largest count before the change. */
+static int heldRecords(SpgpuPrivateHandle* h, const int* rP, int delta)
+{
+    int most = 0, usable = 0;
+    pthread_mutex_lock(&h->formLock);
+    SpgpuAdopted* adopted = NULL;
+    for (int i = 0; h->adopted && i < SPGPU_ADOPTED; ++i)
+        if (h->adopted[i].rows > 0 && h->adopted[i].rP == (const void*)rP)
+            adopted = &h->adopted[i];
+    const void* copy = adopted ? (const void*)adopted->indices : NULL;
+    if (adopted) {
+        most = adopted->holds;
+        usable = 1;
+    }
+    for (int i = 0; i < SPGPU_PLANS; ++i) {
+        SpgpuSpmvPlan* p = &h->plans[i];
+        if (p->rows <= 0 || (p->rP != (const void*)rP && (!copy || p->rP != copy)))
+            continue;
+        most = p->holds > most ? p->holds : most;
+        if (delta > 0 && p->state == SPGPU_PLAN_BUILDING && hipEventSynchronize(p->built) == hipSuccess) {
+            p->deep = ((volatile int*)p->pinned)[0];
+            p->state = SPGPU_PLAN_READY;
+        }
+        usable += p->state == SPGPU_PLAN_READY;
+    }
+    if (delta > 0 && usable > 0) {
+        if (adopted)
+            adopted->holds += 1;
+        for (int i = 0; i < SPGPU_PLANS; ++i) {
+            SpgpuSpmvPlan* p = &h->plans[i];
+            if (p->rows > 0 && p->state == SPGPU_PLAN_READY && (p->rP == (const void*)rP || (copy && p->rP == copy)))
+                p->holds += 1;
+        }
+    } else if (delta > 0) {
+        most = -1; /* nothing to hold */
+    } else if (delta < 0 && most > 0) {
+        if (adopted && adopted->holds > 0)
+            adopted->holds -= 1;
+        for (int i = 0; i < SPGPU_PLANS; ++i) {
+            SpgpuSpmvPlan* p = &h->plans[i];
+            if (p->rows > 0 && p->holds > 0 && (p->rP == (const void*)rP || (copy && p->rP == copy)))
+                p->holds -= 1;
+        }
+    }
+    pthread_mutex_unlock(&h->formLock);
+    return most;
+}
+
+int spgpuSpmvHold(spgpuHandle_t pHandle, const int* rP)
+{
+    if (!pHandle || !rP)
+        return SPGPU_UNSPECIFIED;
+    SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
+    if (!h->plans || !spgpuTuning()->plan)
+        return SPGPU_UNSUPPORTED;
+    /* inside a capture the call neither waits nor touches the stream: the capture goes on undisturbed */
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->pub.currentStream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return SPGPU_UNSUPPORTED;
+    }
+    if (heldRecords(h, rP, 1) < 0)
+        return SPGPU_UNSUPPORTED;
+    (void)hipStreamSynchronize(h->pub.currentStream); /* like Prepare / Freeze / Adopt: what was queued to build the records has landed */
+    return SPGPU_SUCCESS;
+}
+
+int spgpuSpmvRelease(spgpuHandle_t pHandle, const int* rP)
+{
+    if (!pHandle || !rP)
+        return SPGPU_UNSPECIFIED;
+    SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
+    if (!h->plans)
+        return SPGPU_UNSUPPORTED;
+    return heldRecords(h, rP, -1) > 0 ? SPGPU_SUCCESS : SPGPU_UNSUPPORTED;
+}
+
+int spgpuSpmvHolds(spgpuHandle_t pHandle, const int* rP)
+{
+    if (!pHandle || !rP)
+        return 0;
+    SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
+    return h->plans ? heldRecords(h, rP, 0) : 0;
+}
+
 int spgpuSpmvThaw(spgpuHandle_t pHandle, const int* rP)
 {
     SpgpuPrivateHandle* h = spgpuPrivate(pHandle);
     int thawed = 0;
     if (!h || !h->plans || !rP)
         return SPGPU_UNSPECIFIED;
+    if (heldRecords(h, rP, 0) > 0)
+        return SPGPU_IN_USE; /* a captured graph may still replay on the records: nothing is freed */
     {
         /* an adopted matrix: the plan of its ordered copy goes first (keyed by the copy's arrays), then the copy -- behind a
          * device-wide wait: SpMVs in flight read it */

@@ -1435,8 +1435,8 @@ static bool freezeSlab(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<
     return frozen;
 }
 
-/* The SpMV side: a.planPacked / a.packBases of the matrix' frozen record, if it has one (else they stay NULL).  Not inside a
- * stream capture: a graph would carry the copy's address beyond a Thaw. */
+/* The SpMV side: a.planPacked / a.packBases of the matrix' frozen record, if it has one (else they stay NULL).  Inside a stream
+ * capture only a held record (spgpuSpmvHold, include/spgpu/ext/graph.h): a graph would carry the copy's address beyond a Thaw. */
 template <typename T>
 static void findFrozenSlab(spgpuHandle_t handle, hipStream_t stream, SlabArgs<T>& a, int groupRows)
 {
@@ -1446,14 +1446,15 @@ static void findFrozenSlab(spgpuHandle_t handle, hipStream_t stream, SlabArgs<T>
     if (__atomic_load_n(&h->planFrozenSlabs, __ATOMIC_RELAXED) <= 0)
         return;
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
         (void)hipGetLastError();
-        return;
+        capturing = hipStreamCaptureStatusActive;
     }
+    const bool heldOnly = capturing != hipStreamCaptureStatusNone;
     const SpgpuSpmvPlan key = slabPlanKey(a, groupRows);
     spgpuPlanLock(handle);
     SpgpuSpmvPlan* plan = spgpuPlanFind(handle, &key);
-    if (plan && plan->packed && plan->state == SPGPU_PLAN_READY) {
+    if (plan && plan->packed && plan->state == SPGPU_PLAN_READY && (!heldOnly || plan->holds > 0)) {
         a.planPacked = static_cast<const unsigned short*>(plan->packed);
         a.packBases = static_cast<const int*>(plan->device);
         plan->uses += 1;

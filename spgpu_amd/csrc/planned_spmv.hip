@@ -13,7 +13,8 @@
  *   - the launch with a plan: raggedSpmvKernel<..., PLAN> (ragged_spmv.hip.h) over planMainBlocks + ceil(deep / G)
  *     workgroups -- ONE launch, no list, nothing behind it.
  * Both paths add every row's products in the same order (deep_rows.hip.h: chunksOf), so which of them a call takes -- first
- * call, settled, stale plan, captured graph (never planned: a graph outlives a plan) -- does not change a bit of z.
+ * call, settled, stale plan, captured graph (planned only where the plan is held, include/spgpu/ext/graph.h: a graph outlives a
+ * plan the host may retire) -- does not change a bit of z.
  *
  * Roofline: HBM bandwidth.  Algorithmic bytes as for every ELL/HELL SpMV (ellpack_spmv.hip) + 4 per row for rIdx; the plan
  * itself is 32 bytes per 1 024 or 2 048 rows.
@@ -442,14 +443,16 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
 #undef SPGPU_PLANNED_PACKED
     };
 
-    /* a captured launch would carry the plan's addresses for as long as the graph lives; plans are retired: no plan there */
+    /* a captured launch carries the plan's addresses for as long as the graph lives, and plans are retired: in a capture only a
+     * HELD plan (spgpuSpmvHold, include/spgpu/ext/graph.h), which the host never retires, is used -- looked up, never made */
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
         (void)hipGetLastError();
         capturing = hipStreamCaptureStatusActive;
     }
+    const bool heldOnly = capturing != hipStreamCaptureStatusNone;
     bool launched = false;
-    if (tune->plan && in.rIdx && capturing == hipStreamCaptureStatusNone) {
+    if (tune->plan && in.rIdx && (!heldOnly || !prepareOnly)) {
         SpgpuSpmvPlan key{};
         key.rP = in.rP;
         key.rS = in.rS;
@@ -464,15 +467,18 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
         key.subs = subs;
         SpgpuPrivateHandle* h = spgpuPrivate(handle);
         spgpuPlanLock(handle);
-        SpgpuSpmvPlan* plan = spgpuPlanRecord(handle, &key);
+        SpgpuSpmvPlan* plan = heldOnly ? spgpuPlanFind(handle, &key) : spgpuPlanRecord(handle, &key);
+        if (plan && heldOnly && plan->holds <= 0)
+            plan = nullptr;
         if (plan) {
             if (plan->state == SPGPU_PLAN_BUILDING && spgpuEventDone(plan->built)) {
                 plan->deep = ((volatile int*)plan->pinned)[0];
                 plan->state = SPGPU_PLAN_READY;
             }
-            if (plan->state == SPGPU_PLAN_READY && ((volatile int*)plan->pinned)[1] != 0) {
+            if (plan->state == SPGPU_PLAN_READY && plan->holds <= 0 && ((volatile int*)plan->pinned)[1] != 0) {
                 /* a kernel met a sub-group whose depth contradicts the plan: another matrix lives at these addresses now.  (Its
-                 * results were right all the same.)  A matrix that keeps changing under a young plan is left alone after the third time. */
+                 * results were right all the same.)  A matrix that keeps changing under a young plan is left alone after the third time.
+                 * (A held plan cannot go stale: its caller has promised that the index arrays stay as they are.) */
                 h->planStales += 1;
                 plan->stales += 1;
                 const bool giveUp = plan->uses < 16 && plan->stales >= 3;

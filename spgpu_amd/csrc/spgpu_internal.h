@@ -157,14 +157,16 @@ typedef struct SpgpuSpmvPlan {
                      * themselves as 16-bit offsets from the block's packBase, slot for slot as in rP (0xFFFF: ask rP) */
     int* pinned;    /* [0] deep sub-groups, written by the analysis; [1] != 0: a kernel found the plan stale; [2] slots of the index array (freeze) */
     hipEvent_t built;
+    int holds;      /* spgpuSpmvHold (include/spgpu/ext/graph.h): > 0 -- captured launches use the record, the host never retires it */
 } SpgpuSpmvPlan;
 enum { SPGPU_PLAN_EMPTY = 0, SPGPU_PLAN_BUILDING = 1, SPGPU_PLAN_READY = 2, SPGPU_PLAN_GIVEN_UP = 3 };
 /* The plan table is used with the handle's lock held from the look-up to the launch that reads the plan's arrays (a second
  * host thread on the handle may retire a plan and free retired buffers only under the same lock, after a device-wide wait). */
 void spgpuPlanLock(spgpuHandle_t h);
 void spgpuPlanUnlock(spgpuHandle_t h);
-/* Lock held.  The record with this key; or, if there is none, the least recently used record, retired and re-keyed
- * (state EMPTY).  Never NULL once the handle exists (NULL: the handle has no plan table -- its allocation failed). */
+/* Lock held.  The record with this key; or, if there is none, the least recently used record that is not held, retired and
+ * re-keyed (state EMPTY).  NULL: the handle has no plan table (its allocation failed), or every record is held or still being
+ * analysed -- the call runs without a plan. */
 SpgpuSpmvPlan* spgpuPlanRecord(spgpuHandle_t h, const SpgpuSpmvPlan* key);
 /* Lock held.  The record with this key, or NULL (nothing is retired, nothing re-keyed). */
 SpgpuSpmvPlan* spgpuPlanFind(spgpuHandle_t h, const SpgpuSpmvPlan* key);
@@ -180,14 +182,19 @@ typedef struct SpgpuAdopted {
     int* lengths;       /* row lengths in the new order */
     int* order;         /* rIdx: original row of every position */
     long long bytes;    /* device memory of the copy */
+    int holds;          /* spgpuSpmvHold (include/spgpu/ext/graph.h): > 0 -- captured launches run on the copy, Thaw is refused */
 } SpgpuAdopted;
-/* No lock held.  The ordered copy of these arrays, or NULL (none, or the stream is capturing: a graph would outlive the copy). */
+/* No lock held.  The ordered copy of these arrays, or NULL (none, or the stream is capturing and the entry is not held: a graph
+ * would outlive the copy). */
 const SpgpuAdopted* spgpuAdoptedFind(spgpuHandle_t h, hipStream_t stream, const void* cM, const int* rP, const int* rS, const int* hackOffsets,
                                      int rows, int hackSize, int baseIndex, long long valPitch, long long idxPitch);
 /* No lock held.  Takes a free entry for `entry` (copied); SPGPU_UNSUPPORTED when the table is full. */
 int spgpuAdoptedAdd(spgpuHandle_t h, const SpgpuAdopted* entry);
 /* No lock held.  Removes the entries keyed by rP (NULL: all); their arrays are returned in `out` (at most SPGPU_ADOPTED) for the caller to free. */
 int spgpuAdoptedRemove(spgpuHandle_t h, const int* rP, SpgpuAdopted* out);
+
+/* No lock held.  1 when every record of the plan table is held (spgpuSpmvHold): a new matrix gets none. */
+int spgpuPlanTableHeld(spgpuHandle_t h);
 
 /* Lock held.  The plan's device buffer goes to the graveyard (kernels in flight may read it); a full graveyard is emptied
  * after a device-wide wait.  State EMPTY afterwards. */
