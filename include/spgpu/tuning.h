@@ -7,7 +7,6 @@
  * spgpuTuningReload() is called (the A/B tools and the kernel-shape parity
  * tests change them between launches):
  *
- *   SPGPU_SPMV_VARIANT   ELL/HELL SpMV kernel shape (0 = default, see csrc/ellpack_spmv.hip)
  *   SPGPU_NT_LOADS       0: no non-temporal hint on the coefficient/index streams (default 1)
  *   SPGPU_X_STRIPS       ELL/HELL SpMV: x values of a strip of rows with one 16-byte load where the rows name consecutive
  *                        columns.  Unset: learnt per matrix from the kernel's own feedback (csrc/ellpack_spmv.hip);
@@ -163,8 +162,8 @@ int spgpuHellSpmvOptimize(spgpuHandle_t handle, spgpuType_t type, const void* cM
                           const int* rIdx, int rows, int baseIndex);
 
 void spgpuTuningReload(void);
-/* 1 if the library was built with -DSPGPU_TUNING_VARIANTS: the non-default kernel shapes (SPGPU_SPMV_VARIANT, SPGPU_X_TILE_SHAPE,
- * SPGPU_RAGGED_SHAPE, SPGPU_RAGGED=0) exist only in such a build; the product build carries the defaults and ignores those knobs. */
+/* Always 0.  It said whether the library carried the non-default kernel shapes of the lab build, which is retired (their
+ * measurements are kept under profiles/); kept so that existing callers still link. */
 int spgpuTuningVariantsBuilt(void);
 
 /*

@@ -737,7 +737,6 @@ static int envInt(const char* name, int fallback)
 void spgpuTuningReload(void)
 {
     SpgpuTuning t;
-    t.spmvVariant = envInt("SPGPU_SPMV_VARIANT", 0);
     t.ntLoads = envInt("SPGPU_NT_LOADS", 1);
     t.tailLanes = envInt("SPGPU_TAIL_LANES", -1);
     t.hdiaVariant = envInt("SPGPU_HDIA_VARIANT", 0);
@@ -750,14 +749,10 @@ void spgpuTuningReload(void)
     t.xTile = envInt("SPGPU_X_TILE", -1);
     t.autoSweep = envInt("SPGPU_AUTO_SWEEP", 1);
     t.poisonScratch = envInt("SPGPU_POISON_SCRATCH", 0);
-    t.slide = envInt("SPGPU_SLIDE", 0);
-    t.xTileShape = envInt("SPGPU_X_TILE_SHAPE", 0);
     t.deepSplit = envInt("SPGPU_DEEP_SPLIT", -1);
     t.deepCap = envInt("SPGPU_DEEP_CAP", 256);
     t.deepKeep = envInt("SPGPU_DEEP_KEEP", 64);
-    t.ragged = envInt("SPGPU_RAGGED", 1);
     t.raggedShape = envInt("SPGPU_RAGGED_SHAPE", 0);
-    t.pipeGroups = envInt("SPGPU_PIPE_GROUPS", 0);
     t.raggedSplit = envInt("SPGPU_RAGGED_SPLIT", -1);
     t.l1Nt = envInt("SPGPU_L1_NT", -1);
     t.plan = envInt("SPGPU_PLAN", 1);

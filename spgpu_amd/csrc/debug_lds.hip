@@ -1,5 +1,5 @@
 /*
- * Lab builds only (-DSPGPU_TUNING_VARIANTS): spgpuDebugFillLds(handle, word) fills the LDS of every CU with one 32-bit word (0; or ~0: -1 as an
+ * Debug builds only (-DSPGPU_DEBUG): spgpuDebugFillLds(handle, word) fills the LDS of every CU with one 32-bit word (0; or ~0: -1 as an
  * integer, NaN as a float or double) on the handle's current stream.  LDS is not cleared between workgroups: a kernel that reads a word of it before writing it finds what the last
  * workgroup on that CU left there -- in a loop over one matrix the right values of the previous launch, which hides the slip.
  * tools/stress_lds.py runs the ordered SpMV paths with this in front of every call; no product path calls it.
@@ -8,7 +8,7 @@
 
 #include "spgpu/core.h"
 
-#ifdef SPGPU_TUNING_VARIANTS
+#ifdef SPGPU_DEBUG
 namespace {
 
 constexpr int kLdsBytes = 80 * 1024; /* two such workgroups hold the CU's 160 KiB */

@@ -74,6 +74,7 @@ __device__ inline long long sampleGroup(long long groups, int q)
  * PH     phases: lane groups that split the entries of a row by k mod PH
  *        (PH == 1: a lane walks all entries of its rows, no cross-lane sum)
  * UNROLL slab-column loads issued back to back before the first gather
+ * PIPE   the next stage is prefetched while the current one is consumed (every kernel but the lean one, launchLean)
  * One wavefront owns 64/PH strips = (64/PH)*RPL consecutive rows.
  * STRIPS compiles the strip-load form in (see consume below); the form without it exists as well because the mere
  *        presence of the second loop costs the gather loop ~8 % on scattered matrices (measured; same instruction
@@ -83,14 +84,14 @@ __device__ inline long long sampleGroup(long long groups, int q)
  *        slot as in rP; 0xFFFF = "ask rP") -- 2 bytes per stored entry instead of 4.  Same columns, same order: same bits.  The
  *        rare paths (whole-wave tail rows, the sample wavefronts' span) read rP itself, which the caller's promise keeps valid.
  */
-template <typename T, int RPL, int PH, bool IS_HELL, bool NT, int UNROLL, int PIPE, bool TAIL, int XPOLICY = 0, bool STRIPS = false,
-          int BLOCK = kBlockThreads, int TILE_BYTES = 0, bool DEEP = false, int GPW = 1, int TAIL_EVERY = 0, bool PACKED = false>
+template <typename T, int RPL, int PH, bool IS_HELL, bool NT, int UNROLL, bool PIPE, bool TAIL, bool STRIPS = false,
+          int BLOCK = kBlockThreads, int TILE_BYTES = 0, int TAIL_EVERY = 0, bool PACKED = false>
 __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
 {
     /* (PACKED, measured: the fp64 kernel needs 140 VGPRs -- 3 wavefronts per SIMD, as the unpacked kernel's 146.  Capped at 128 for a
      * fourth wavefront -- amdgpu_waves_per_eu(4, 4) -- it spills 52-64 bytes per lane into its stage loop: 0.575 -> 0.896 ms; with
      * the stage consumed in two halves (16 instead of 32 registers of x alive) 56-152 bytes still.) */
-    static_assert(!PACKED || (TILE_BYTES == 0 && !DEEP && RPL >= 2 && XPOLICY == 0), "packed indices: the gather and strip forms of 4- and 8-byte elements");
+    static_assert(!PACKED || (TILE_BYTES == 0 && RPL >= 2), "packed indices: the gather and strip forms of 4- and 8-byte elements");
     using ColumnWord = typename std::conditional<PACKED, unsigned short, int>::type;
     constexpr int LPC = kWave / PH;         /* lanes that cover one slab column */
     constexpr int GROUP_ROWS = LPC * RPL;   /* rows owned by the wavefront */
@@ -102,15 +103,9 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
     const int sub = lane % LPC;   /* which RPL-row strip of the group */
     const int phase = lane / LPC; /* which residue class of k */
     const T* __restrict__ x = a.x;
-
-    /* GPW groups per wavefront (x-tile forms: 2).  A workgroup owns GPW * WAVES consecutive groups and wavefront w takes
-     * the groups w and 2 * WAVES - 1 - w: when the rows were ordered by length the depths along a workgroup's groups
-     * rise or fall monotonically, and pairing the two ends gives every wavefront about the same work -- the tile stays
-     * allocated until the slowest wavefront is done.  It also halves the tile fills per row. */
-    static_assert(GPW == 1 || GPW == 2, "one group per wavefront, or the two ends of the workgroup's range");
-    auto groupOfTurn = [&](int turn) -> long long {
+    auto groupOf = [&]() -> long long { /* the group of rows this wavefront owns */
         const int wave = threadIdx.x >> 6;
-        return (long long)blockIdx.x * (WAVES * GPW) + (turn == 0 ? wave : 2 * WAVES - 1 - wave);
+        return (long long)blockIdx.x * WAVES + wave;
     };
 
     /* XTILE: x[tileBase .. tileBase + tileCount) lives in `tile` once the prologue below has run */
@@ -125,10 +120,11 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
          * centred on the mean of the rows' middles (a few far-away rows then do not drag it off). */
         ColumnProbe mine{0x7fffffff, -0x7fffffff - 1, 0, 0};
         if (phase == 0) {
-            int first[GPW][RPL], last[GPW][RPL], lenAt[GPW][RPL];
+            int first[RPL], last[RPL], lenAt[RPL];
+            /* (a one-trip loop for the same reason as the one around processGroup below) */
 #pragma unroll
-            for (int turn = 0; turn < GPW; ++turn) {
-                const long long r0 = groupOfTurn(turn) * GROUP_ROWS + (long long)sub * RPL;
+            for (int once = 0; once < 1; ++once) {
+                const long long r0 = groupOf() * GROUP_ROWS + (long long)sub * RPL;
                 long long at = 0;
                 if (r0 < a.rows) {
                     if constexpr (IS_HELL) {
@@ -141,23 +137,20 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
 #pragma unroll
                 for (int t = 0; t < RPL; ++t) {
                     const long long r = r0 + t;
-                    lenAt[turn][t] = r < a.rows ? (a.rS ? a.rS[r] : a.maxNnz) : 0;
-                    first[turn][t] = lenAt[turn][t] > 0 ? a.rP[at + t] : 0;
-                    last[turn][t] = lenAt[turn][t] > 0 ? a.rP[at + t + (long long)(lenAt[turn][t] - 1) * a.idxStride] : 0;
+                    lenAt[t] = r < a.rows ? (a.rS ? a.rS[r] : a.maxNnz) : 0;
+                    first[t] = lenAt[t] > 0 ? a.rP[at + t] : 0;
+                    last[t] = lenAt[t] > 0 ? a.rP[at + t + (long long)(lenAt[t] - 1) * a.idxStride] : 0;
                 }
             }
 #pragma unroll
-            for (int turn = 0; turn < GPW; ++turn) {
-#pragma unroll
-                for (int t = 0; t < RPL; ++t) {
-                    if (lenAt[turn][t] > 0) {
-                        const int f = first[turn][t] - a.baseIndex, l = last[turn][t] - a.baseIndex;
-                        const int low = f < l ? f : l, high = f < l ? l : f;
-                        mine.lowest = low < mine.lowest ? low : mine.lowest;
-                        mine.highest = high > mine.highest ? high : mine.highest;
-                        mine.middles += ((long long)f + l) >> 1;
-                        mine.rows += 1;
-                    }
+            for (int t = 0; t < RPL; ++t) {
+                if (lenAt[t] > 0) {
+                    const int f = first[t] - a.baseIndex, l = last[t] - a.baseIndex;
+                    const int low = f < l ? f : l, high = f < l ? l : f;
+                    mine.lowest = low < mine.lowest ? low : mine.lowest;
+                    mine.highest = high > mine.highest ? high : mine.highest;
+                    mine.middles += ((long long)f + l) >> 1;
+                    mine.rows += 1;
                 }
             }
         }
@@ -243,34 +236,6 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
         len[t] = r < a.rows ? (a.rS ? a.rS[r] : a.maxNnz) : 0;
         laneLongest = len[t] > laneLongest ? len[t] : laneLongest;
     }
-    /* DEEP: one very long row (or a hack of them, after the rows were ordered by length) would keep this wavefront
-     * streaming long after the rest of the grid has drained -- a single wavefront moves a few GB/s.  A 32-row
-     * sub-group deeper than deepCap therefore keeps only its first deepCap columns here; it registers itself in the
-     * deep list and the deep kernels, launched right behind this kernel, spread the remaining columns -- in chunks,
-     * a wavefront each -- add the sums below and write z.  A full list: the sub-group stays here. */
-    int deepSlot = -1;
-    if constexpr (DEEP) {
-        static_assert(PH == 1, "the deep split is built for the shapes in which a lane walks whole rows");
-        constexpr int SUB = 32 / RPL; /* lanes that hold one 32-row sub-group */
-        int subDepth = laneLongest;
-#pragma unroll
-        for (int m = 1; m < SUB; m <<= 1) {
-            const int other = laneXor(subDepth, m);
-            subDepth = other > subDepth ? other : subDepth;
-        }
-        int slot = -1;
-        if (lane % SUB == 0 && subDepth > a.deepCap)
-            slot = deepRegister(a, (int)row0, subDepth, (unsigned)slab);
-        deepSlot = __shfl(slot, lane & ~(SUB - 1), kWave);
-        if (deepSlot >= 0) {
-            laneLongest = 0;
-#pragma unroll
-            for (int t = 0; t < RPL; ++t) {
-                len[t] = len[t] < a.deepKeep ? len[t] : a.deepKeep;
-                laneLongest = len[t] > laneLongest ? len[t] : laneLongest;
-            }
-        }
-    }
     const int groupLongest = waveMax(laneLongest); /* wave-uniform trip count */
 
     T sum[RPL];
@@ -287,8 +252,8 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
 
     /* One stage = UNROLL slab columns per phase: the coefficient/index loads of a stage are
      * issued back to back (fetch), its x gathers and multiply-adds follow (consume).  With
-     * PIPE the next stage is fetched BEFORE the current one is consumed, so the stream loads
-     * of stage s+1 are in flight while the gathers of stage s wait for x. */
+     * PIPE the next stage is fetched right behind the current stage's x loads, so the stream
+     * loads of stage s+1 are in flight while the gathers of stage s wait for x. */
     struct Stage {
         Pack<T, RPL> v[UNROLL];
         Pack<ColumnWord, RPL> c[UNROLL];
@@ -379,7 +344,7 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
                 for (int t = 0; t < RPL; ++t) {
                     const int col = columnOf(s, u, t, k);
                     use[u][t] = k < len[t] && col >= 0;
-                    xv[u][t] = loadX<XPOLICY>(x + (use[u][t] ? col : 0));
+                    xv[u][t] = x[use[u][t] ? col : 0];
                 }
             }
         }
@@ -456,7 +421,7 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
         }
         return false;
     };
-    constexpr bool STRIPS_POSSIBLE = STRIPS && RPL > 1 && XPOLICY == 0;
+    constexpr bool STRIPS_POSSIBLE = STRIPS && RPL > 1;
     int kBase = 0;
     bool done = false; /* tail taken */
     if constexpr (PIPE) {
@@ -464,13 +429,9 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
         fetch(0, cur);
         /* one stage: `form` says how its x values are fetched */
         auto stage = [&](auto form) {
-            if constexpr (PIPE == 2) {
-                /* prefetch issued after the current x loads: younger in vmcnt order, stays in flight */
-                consume(form, kBase, cur, [&] { fetch(kBase + STEP, nxt); });
-            } else {
-                fetch(kBase + STEP, nxt); /* lanes past their rows' end fetch nothing */
-                consume(form, kBase, cur, [] {});
-            }
+            /* prefetch issued after the current x loads: younger in vmcnt order, stays in flight; lanes past their rows'
+             * end fetch nothing */
+            consume(form, kBase, cur, [&] { fetch(kBase + STEP, nxt); });
             cur = nxt;
         };
         if constexpr (STRIPS_POSSIBLE) {
@@ -574,15 +535,6 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
     if (phase != 0 || !stripLive)
         return;
 
-    if constexpr (DEEP) {
-        if (deepSlot >= 0) { /* raw sums: deepFinishKernel finishes these rows */
-#pragma unroll
-            for (int t = 0; t < RPL; ++t)
-                a.deepPartials[(size_t)deepSlot * 32 + (size_t)((row0 + t) & 31)] = sum[t];
-            return;
-        }
-    }
-
     const bool hasBeta = isNotZero(a.beta);
     if (!a.rIdx && a.wideIO && row0 + RPL <= a.rows) {
         Pack<T, RPL> out;
@@ -610,13 +562,15 @@ __global__ __launch_bounds__(BLOCK) void slabSpmvKernel(const SlabArgs<T> a)
     }
     }; /* processGroup */
 
-#pragma unroll 1
-    for (int turn = 0; turn < GPW; ++turn)
-        processGroup(groupOfTurn(turn));
+    /* One group per wavefront.  The one-trip loop (and groupOf evaluated here again) is kept for the code it compiles to:
+     * called straight, processGroup comes out with other registers and another instruction order in every slab kernel --
+     * a change of its own, for its own A/B. */
+    for (int once = 0; once < 1; ++once)
+        processGroup(groupOf());
 }
 
 /*
- * The columns >= deepCap of the sub-groups (32 rows) a DEEP main kernel registered, in two launches right behind it.
+ * The columns >= deepCap of the sub-groups (32 rows) the queue kernel registered (raggedSpmvKernel, DEEP), in two launches right behind it.
  *
  * deepItemsKernel: a wavefront per item, an item = CHUNK columns of one sub-group.  The wavefront reads the chunk the
  * way the format stores it -- 32/RPL lanes with RPL rows each cover a slab column, PH = 64 / (32/RPL) columns per load
@@ -1132,11 +1086,6 @@ __global__ __launch_bounds__(kBlockThreads) void sweepSpmvKernel(const SlabArgs<
 __device__ unsigned long long* spgpuTraceBuffer;
 #endif
 #include "ragged_spmv.hip.h"
-#ifdef SPGPU_TUNING_VARIANTS
-#include "slide_spmv.hip.h"
-#include "share_spmv.hip.h"
-#include "pipe_spmv.hip.h"
-#endif
 
 /* ---- host side ----------------------------------------------------------- */
 
@@ -1145,74 +1094,49 @@ static bool alignedTo(const void* p, size_t bytes)
     return ((uintptr_t)p % bytes) == 0;
 }
 
-template <typename T, int RPL, int PH, bool IS_HELL, int UNROLL, int PIPE = 0, bool TAIL = false, int XPOLICY = 0, bool STRIPS = false,
-          int BLOCK = kBlockThreads, int TILE_BYTES = 0>
+/* The gather and strip forms (launchSlabFamily): the next stage prefetched behind the current gathers. */
+template <typename T, int RPL, int PH, bool IS_HELL, int UNROLL, bool TAIL, bool STRIPS = false>
 static void launchSlab(hipStream_t stream, const SlabArgs<T>& a, bool nt)
 {
     constexpr int GROUP_ROWS = (kWave / PH) * RPL;
-    constexpr int WAVES = BLOCK / kWave;
+    constexpr int WAVES = kBlockThreads / kWave;
     const long long groups = ((long long)a.rows + GROUP_ROWS - 1) / GROUP_ROWS;
     const unsigned blocks = (unsigned)((groups + WAVES - 1) / WAVES);
     if (nt)
-        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, PIPE, TAIL, XPOLICY, STRIPS, BLOCK, TILE_BYTES>),
-                           dim3(blocks), dim3(BLOCK), 0, stream, a);
+        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, true, TAIL, STRIPS>), dim3(blocks), dim3(kBlockThreads), 0, stream, a);
     else
-        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, false, UNROLL, PIPE, TAIL, XPOLICY, STRIPS, BLOCK, TILE_BYTES>),
-                           dim3(blocks), dim3(BLOCK), 0, stream, a);
+        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, false, UNROLL, true, TAIL, STRIPS>), dim3(blocks), dim3(kBlockThreads), 0, stream, a);
 }
 
 /* The x-tile forms.  Workgroup size and tile size go together: the tile has to hold the columns of the workgroup's
- * rows, and LDS (160 KiB per CU) divided by the tile is the number of workgroups a CU overlaps.  A lane walks whole
- * rows (PH 1) with 4 slab columns per stage -- half the stage of the gather kernel: LDS gathers are short, and at 8 the
- * kernel needs 148 VGPRs, which leaves room for one 512-lane workgroup per CU only.  Shape 0 is the default; the
- * others exist for A/B runs (SPGPU_X_TILE_SHAPE):
- *   1  one wavefront per 32-row group (PH = 2 * RPL, 2 columns per stage), 512 lanes, 64 KiB  (no deep split)
- *   2  512 lanes, 64 KiB      3  256 lanes, 48 KiB
- * The coefficient/index streams always carry the non-temporal hint here. */
-template <typename T, int RPL, int PH, bool IS_HELL, int UNROLL, bool TAIL, int BLOCK, int TILE_BYTES, bool DEEP, int GPW = 1,
-          int TAIL_EVERY = 0>
+ * rows, and LDS (160 KiB per CU) divided by the tile is the number of workgroups a CU overlaps.  The coefficient/index
+ * streams always carry the non-temporal hint here. */
+template <typename T, int RPL, int PH, bool IS_HELL, int UNROLL, bool TAIL, int BLOCK, int TILE_BYTES, int TAIL_EVERY = 0>
 static void launchShape(hipStream_t stream, const SlabArgs<T>& a)
 {
     constexpr int GROUP_ROWS = (kWave / PH) * RPL;
     constexpr int WAVES = BLOCK / kWave;
     const long long groups = ((long long)a.rows + GROUP_ROWS - 1) / GROUP_ROWS;
-    const unsigned blocks = (unsigned)((groups + WAVES * GPW - 1) / (WAVES * GPW));
-    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, 2, TAIL, 0, false, BLOCK, TILE_BYTES, DEEP, GPW, TAIL_EVERY>),
+    const unsigned blocks = (unsigned)((groups + WAVES - 1) / WAVES);
+    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, true, TAIL, false, BLOCK, TILE_BYTES, TAIL_EVERY>),
                        dim3(blocks), dim3(BLOCK), 0, stream, a);
 }
 
-template <typename T, int RPL, bool IS_HELL, bool DEEP>
-static void launchTiled(hipStream_t stream, const SlabArgs<T>& a, int shape)
+/* Same summation order as the type's gather / strip kernel (launchSlabFamily), so that the form AUTO settles on never
+ * changes a bit of the result: 8-byte elements walk whole rows and consider the tail every 8 columns; fp32 keeps its
+ * 8 phases x 2 columns; complex fp64 its 2 phases.  Otherwise a lane walks whole rows (PH 1) with 4 slab columns per
+ * stage -- half the stage of the gather kernel: LDS gathers are short, and at 8 the kernel needs 148 VGPRs, which leaves
+ * room for one 512-lane workgroup per CU only.  32 KiB of x per workgroup. */
+template <typename T, int RPL, bool IS_HELL>
+static void launchTiled(hipStream_t stream, const SlabArgs<T>& a)
 {
-    constexpr int PH1 = (sizeof(T) == 16 && !DEEP) ? 2 : 1; /* 16-byte elements keep the 2-phase shape of their default kernel */
-    constexpr bool TAIL = PH1 == 1;
-    switch (shape) {
-#ifdef SPGPU_TUNING_VARIANTS
-    case 1:
-        if constexpr (!DEEP) {
-            launchShape<T, RPL, (RPL > 1 ? 2 * RPL : 2), IS_HELL, (RPL > 1 ? 2 : 4), (RPL > 1), 512, 65536, false>(stream, a);
-            break;
-        }
-        [[fallthrough]];
-    case 2: launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 512, 65536, DEEP>(stream, a); break;
-    case 3: launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 256, 49152, DEEP, 2>(stream, a); break;
-    case 4: launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 256, 65536, DEEP, 2>(stream, a); break;
-    case 5: launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 512, 65536, DEEP, 2>(stream, a); break;
-#endif
-    default:
-        /* the default: same summation order as the type's gather / strip kernel (launchSlabFamily), so that the form
-         * AUTO settles on never changes a bit of the result: 8-byte elements walk whole rows and consider the tail every
-         * 8 columns; fp32 keeps its 8 phases x 2 columns; complex fp64 its 2 phases */
-        if constexpr (DEEP)
-            launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 256, 32768, true>(stream, a);
-        else if constexpr (sizeof(T) == 4 && RPL == 4)
-            launchShape<T, RPL, 2 * RPL, IS_HELL, 2, true, 512, 32768, false>(stream, a);
-        else if constexpr (sizeof(T) == 8 && RPL == 2)
-            launchShape<T, RPL, 1, IS_HELL, 4, true, 256, 32768, false, 1, 8>(stream, a);
-        else
-            launchShape<T, RPL, PH1, IS_HELL, 4, TAIL, 256, 32768, false>(stream, a);
-        break;
-    }
+    constexpr int PH = sizeof(T) == 16 ? 2 : 1; /* the phases of the narrow kernels: whole-wave tail rows with one phase only */
+    if constexpr (sizeof(T) == 4 && RPL == 4)
+        launchShape<T, RPL, 2 * RPL, IS_HELL, 2, true, 512, 32768>(stream, a);
+    else if constexpr (sizeof(T) == 8 && RPL == 2)
+        launchShape<T, RPL, 1, IS_HELL, 4, true, 256, 32768, 8>(stream, a);
+    else
+        launchShape<T, RPL, PH, IS_HELL, 4, PH == 1, 256, 32768>(stream, a);
 }
 
 constexpr int kAutoSweepRows = 2 * 1024 * 1024; /* AUTO: the SWEEP form wants a grid that fills the chip (8 192 rows per workgroup); measured, scattered
@@ -1254,7 +1178,7 @@ static void launchLean(hipStream_t stream, const SlabArgs<T>& a)
     constexpr int WAVES = kBlockThreads / kWave;
     const long long groups = ((long long)a.rows + GROUP_ROWS - 1) / GROUP_ROWS;
     const unsigned blocks = (unsigned)((groups + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, 1, IS_HELL, true, 4, 0, true, 0, false, kBlockThreads, 0, false, 1, 8>), dim3(blocks),
+    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, 1, IS_HELL, true, 4, false, true, false, kBlockThreads, 0, 8>), dim3(blocks),
                        dim3(kBlockThreads), 0, stream, a);
 }
 
@@ -1470,7 +1394,7 @@ static void launchSlabPacked(hipStream_t stream, const SlabArgs<T>& a)
     constexpr int WAVES = kBlockThreads / kWave;
     const long long groups = ((long long)a.rows + GROUP_ROWS - 1) / GROUP_ROWS;
     const unsigned blocks = (unsigned)((groups + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, 2, true, 0, STRIPS, kBlockThreads, 0, false, 1, 0, true>),
+    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, true, true, STRIPS, kBlockThreads, 0, 0, true>),
                        dim3(blocks), dim3(kBlockThreads), 0, stream, a);
 }
 
@@ -1498,29 +1422,16 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
     const bool wideOk = layoutOk && alignedTo(a.cM, 16) && alignedTo(a.rP, 4 * WIDE) &&
                         a.valStride % WIDE == 0 && a.idxStride % WIDE == 0;
 
-    /* Kernel shape.  Measured on MI355X, 10 M rows x 32 nnz (tools/sweep_hell.py, profiles/): D/C stream
-     * fastest with a lane walking whole rows, 8 slab columns per stage, the next stage prefetched AFTER
-     * the current gathers are issued, and whole-wave tail rows (banded 5.9 TB/s, windowed columns +13 %
-     * over prefetch-before); S with 8 phases x 2 columns, same prefetch and tail (5.4-6.0 TB/s); 16-byte
-     * elements (Z) and unaligned streams take RPL = 1 with 2 phases x 4 columns (5.9 TB/s).
-     * SPGPU_SPMV_VARIANT (experiments; 0 = this table):
-     *   1 wide PHx2 | 2 wide 1x4 | 3 narrow 2x4 | 4 narrow 1x4 | 6 wide PHx2 pipe | 12 wide 1x8 pipe |
-     *   13 narrow 2x4 pipe | 17 wide 1x8 pipe + whole-wave tail rows | 18 wide PHx2 pipe + tail rows |
-     *   21 = 17 and 22 = 18 with the prefetch issued after the gathers (defaults for D/C and S)
-     *   (5,7..11,14..16 exist only in -DSPGPU_TUNING_VARIANTS builds)
-     * SPGPU_NT_LOADS 0/1: non-temporal hint on the coefficient/index streams (default 1). */
+    /* Kernel shape.  Measured on MI355X, 10 M rows x 32 nnz (profiles/): wide where the layout allows it (wideOk), with the
+     * next stage prefetched AFTER the current gathers are issued and whole-wave tail rows -- D/C fastest with a lane walking
+     * whole rows, 8 slab columns per stage (banded 5.9 TB/s, windowed columns +13 % over prefetch-before); S (PHASED) with
+     * 8 phases x 2 columns (5.4-6.0 TB/s).  16-byte elements (Z) and unaligned streams run narrow: RPL = 1 with 2 phases
+     * x 4 columns (5.9 TB/s).  SPGPU_NT_LOADS 0/1: non-temporal hint on the coefficient/index streams (default 1). */
+    constexpr bool PHASED = sizeof(T) == 4;
+    constexpr int WIDE_GROUP_ROWS = PHASED ? (kWave / (2 * WIDE)) * WIDE : kWave * WIDE; /* rows of a wavefront of the wide kernel */
     const SpgpuTuning* tune = spgpuTuning();
     a.tailLanes = tune->tailLanes >= 0 ? tune->tailLanes : kTailLanes;
-    int variant = tune->spmvVariant;
     const bool nt = tune->ntLoads != 0;
-#ifndef SPGPU_TUNING_VARIANTS
-    variant = 0; /* the product build carries the default shapes only (13, 21, 22); the others: -DSPGPU_TUNING_VARIANTS */
-#endif
-    if (variant < 1 || variant > 24)
-        variant = !wideOk ? 13 : (sizeof(T) == 4 ? 22 : 21);
-    const bool narrowVariant = variant == 3 || variant == 4 || (variant >= 13 && variant <= 16);
-    if (!wideOk && !narrowVariant)
-        variant = 13;
 
     /* Strip x loads (consume<STRIPS>): which form a matrix runs in is learnt from the kernel itself.  The
      * strip-capable kernel's sample wavefronts write "ran as strips / as gathers" into pinned host memory; a
@@ -1535,7 +1446,7 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
         form = tune->xTile ? SPGPU_SPMV_FORM_XTILE : (form == SPGPU_SPMV_FORM_XTILE ? SPGPU_SPMV_FORM_AUTO : form);
     if (form == SPGPU_SPMV_FORM_SWEEP) {
         /* the caller's choice for scattered columns that ascend inside a row; needs 16-byte slab accesses and no row order */
-        if (wideOk && !a.rIdx && tune->spmvVariant < 1) {
+        if (wideOk && !a.rIdx) {
             if (prepared)
                 return;
             a.wideIO = alignedTo(a.z, 16) && alignedTo(a.y, 16);
@@ -1546,27 +1457,10 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
         }
         form = SPGPU_SPMV_FORM_AUTO;
     }
-#ifdef SPGPU_TUNING_VARIANTS
-    if (tune->slide && form != SPGPU_SPMV_FORM_SWEEP) {
-        /* experiment (SPGPU_SLIDE=1, lab build only; slide_spmv.hip.h, profiles/r04_exp_slide_tile.txt): the x tile moves along with
-         * the slab columns; 8-byte elements, 16-byte slab accesses, no row order.  One phase, no whole-wave tail rows: the order
-         * of additions of the SWEEP form. */
-        if constexpr (sizeof(T) == 8) {
-            if (wideOk && !a.rIdx && tune->spmvVariant < 1 && !prepared) {
-                a.wideIO = alignedTo(a.z, 16) && alignedTo(a.y, 16);
-                a.feedback = nullptr;
-                spgpuNoteSpmvForm(handle, SPGPU_SPMV_FORM_XTILE);
-                launchSlide<T, WIDE, IS_HELL>(stream, a);
-                return;
-            }
-        }
-    }
-#endif
-    const bool tiled = form == SPGPU_SPMV_FORM_XTILE && (variant == 13 || variant == 21 || variant == 22);
-    /* Deep split (see slabSpmvKernel, DEEP): on when the caller passes a row order -- rows ordered by length are what
+    const bool tiled = form == SPGPU_SPMV_FORM_XTILE;
+    /* Deep split (ragged_spmv.hip.h, the deep list): on when the caller passes a row order -- rows ordered by length are what
      * one does to a ragged matrix, and then whole hacks are deep -- or when SPGPU_DEEP_SPLIT says so. */
-    bool deepSplit = (tune->deepSplit >= 0 ? tune->deepSplit != 0 : a.rIdx != nullptr) && wideOk &&
-                     (variant == 21 || variant == 22);
+    bool deepSplit = (tune->deepSplit >= 0 ? tune->deepSplit != 0 : a.rIdx != nullptr) && wideOk;
     a.deepCap = tune->deepCap > 0 ? tune->deepCap : 256;
     a.deepKeep = tune->deepKeep >= 0 && tune->deepKeep < a.deepCap ? tune->deepKeep : a.deepCap;
     a.xcdRun = tune->xcdOrder;
@@ -1593,35 +1487,10 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
             noDeepList = true;
         }
     }
-#ifdef SPGPU_TUNING_VARIANTS /* two stateless one-launch kernels of round 3, kept for A/B runs (another order of additions: chunks of 48 columns) */
-    if (prepared && (tune->ragged == 2 || tune->ragged == 3))
-        return;
-    if (a.rIdx != nullptr && wideOk && (variant == 21 || variant == 22) && tune->ragged == 3) {
-        /* rows ordered by length: one resident workgroup per CU, the next block prepared beside the stream (pipe_spmv.hip.h) */
-        a.wideIO = 0;
-        a.feedback = nullptr;
-        spgpuNoteSpmvForm(handle, form != SPGPU_SPMV_FORM_GATHER ? SPGPU_SPMV_FORM_XTILE : SPGPU_SPMV_FORM_GATHER);
-        launchPipe<T, WIDE, IS_HELL>(stream, a, tune->pipeGroups > 0 ? tune->pipeGroups : handle->multiProcessorCount, form != SPGPU_SPMV_FORM_GATHER, tune->raggedShape);
-        return;
-    }
-    if (a.rIdx != nullptr && wideOk && (variant == 21 || variant == 22) && tune->ragged == 2) {
-        /* rows ordered by length: shares of equal work, one launch, no state (share_spmv.hip.h) */
-        a.wideIO = 0;
-        a.feedback = nullptr;
-        spgpuNoteSpmvForm(handle, form != SPGPU_SPMV_FORM_GATHER ? SPGPU_SPMV_FORM_XTILE : SPGPU_SPMV_FORM_GATHER);
-        launchShare<T, WIDE, IS_HELL>(stream, a, tune->raggedShape, form != SPGPU_SPMV_FORM_GATHER);
-        return;
-    }
-#endif
     /* ELL says how long its longest row is: when none can exceed the cap nothing registers and the two launches behind
      * the main kernel (~5 us each when empty) are left out; HELL does not say */
     const bool deepPossible = IS_HELL || a.maxNnz > a.deepCap;
-#ifndef SPGPU_TUNING_VARIANTS
-    constexpr bool queueKernelOnly = true; /* the deep split with fixed rows per wavefront (SPGPU_RAGGED=0) is a lab shape */
-#else
-    constexpr bool queueKernelOnly = false;
-#endif
-    if ((deepSplit || noDeepList) && (tune->ragged != 0 || queueKernelOnly)) {
+    if (deepSplit || noDeepList) {
         /* the queue-driven kernel for rows ordered by length (ragged_spmv.hip.h); x through an LDS tile unless the
          * caller asked for plain gathers */
         a.wideIO = 0;
@@ -1674,30 +1543,15 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
         /* (the forms below learn what they need from their own launches) -- Freeze of a matrix without a row order: the default
          * kernels' 16-bit index copy */
         if constexpr (WIDE > 1) {
-            if (freeze && !a.rIdx && wideOk && !narrowVariant && !tiled && nt && (variant == 21 || variant == 22) && !deepSplit)
-                *prepared = freezeSlab<T, IS_HELL>(handle, stream, a, variant == 22 ? (kWave / (2 * WIDE)) * WIDE : kWave * WIDE) ? 1 : 0;
+            if (freeze && !a.rIdx && wideOk && !tiled && nt)
+                *prepared = freezeSlab<T, IS_HELL>(handle, stream, a, WIDE_GROUP_ROWS) ? 1 : 0;
         }
         return;
     }
-#ifdef SPGPU_TUNING_VARIANTS
-    if (deepSplit) {
-        /* shapes in which a lane walks whole rows, for every type; the strip form does not apply to ordered rows */
-        a.wideIO = alignedTo(a.z, 16) && alignedTo(a.y, 16);
-        a.feedback = nullptr;
-        spgpuNoteSpmvForm(handle, tiled ? SPGPU_SPMV_FORM_XTILE : SPGPU_SPMV_FORM_GATHER);
-        if (tiled)
-            launchTiled<T, WIDE, IS_HELL, true>(stream, a, tune->xTileShape);
-        else
-            launchShape<T, WIDE, 1, IS_HELL, (sizeof(T) == 8 ? 8 : 4), true, kBlockThreads, 0, true>(stream, a);
-        if (deepPossible)
-            launchDeep<T, WIDE, IS_HELL>(stream, a);
-        return;
-    }
-#endif
     bool strips = false, autoTile = false, autoSweep = false, probeBehind = false;
     a.feedback = nullptr;
-    a.tileSpanLimit = (long long)(32768 / sizeof(T)) * 5 / 4; /* 1.25 x the default tile (launchTiled, shape 0) */
-    if (!narrowVariant && WIDE > 1 && !tiled) {
+    a.tileSpanLimit = (long long)(32768 / sizeof(T)) * 5 / 4; /* 1.25 x the tile (launchTiled) */
+    if (wideOk && WIDE > 1 && !tiled) {
         if (form != SPGPU_SPMV_FORM_AUTO) {
             strips = form == SPGPU_SPMV_FORM_STRIPS;
         } else {
@@ -1713,12 +1567,11 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
             }
             /* two of three samples decide: scattered -> gathers; inside a window -> the LDS tile; otherwise (strips, or
              * nothing known yet) the strip-capable kernel */
-            autoTile = local >= 2 && tune->spmvVariant < 1 && (variant == 21 || variant == 22);
+            autoTile = local >= 2;
             strips = gathers + local + sweeps < 2;
             /* scattered over all of x, ascending inside the rows, rows about equally long (only the probe says so: answer 4):
              * the SWEEP form -- same bits as the default kernel of the 8-byte types; it needs rows for a resident grid */
-            autoSweep = sweeps >= 2 && !autoTile && sizeof(T) == 8 && variant == 21 && tune->spmvVariant < 1 && tune->autoSweep != 0 &&
-                        !a.rIdx && a.rows >= kAutoSweepRows;
+            autoSweep = sweeps >= 2 && !autoTile && sizeof(T) == 8 && tune->autoSweep != 0 && !a.rIdx && a.rows >= kAutoSweepRows;
             a.feedback = seen; /* the strip-capable kernel's sample wavefronts report (it is what a new matrix runs first) */
             /* the other forms do not (see slabSpmvKernel): with every fourth call of theirs three wavefronts look at the
              * matrix again -- another one may live at this address by now -- and with the first of them (the samples know
@@ -1741,91 +1594,43 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
     }
     if (!strips)
         a.feedback = nullptr;
-    if (!narrowVariant) {
+    if (wideOk) {
         a.wideIO = alignedTo(a.z, 16) && alignedTo(a.y, 16);
         if constexpr (WIDE > 1) {
-            switch (variant) {
-#ifdef SPGPU_TUNING_VARIANTS
-            case 1: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 2>(stream, a, nt); break;
-            case 2: launchSlab<T, WIDE, 1, IS_HELL, 4>(stream, a, nt); break;
-            case 6: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 2, true>(stream, a, nt); break;
-            case 12: launchSlab<T, WIDE, 1, IS_HELL, 8, true>(stream, a, nt); break;
-            case 17: launchSlab<T, WIDE, 1, IS_HELL, 8, 1, true>(stream, a, nt); break;
-            case 18: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 2, true, true>(stream, a, nt); break;
-            case 5: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 4>(stream, a, nt); break;
-            case 7: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 4, true>(stream, a, nt); break;
-            case 8: launchSlab<T, WIDE, 1, IS_HELL, 4, true>(stream, a, nt); break;
-            case 9: launchSlab<T, WIDE, 1, IS_HELL, 8>(stream, a, nt); break;
-            case 10: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 1, true>(stream, a, nt); break;
-            case 11: launchSlab<T, WIDE, 1, IS_HELL, 2, true>(stream, a, nt); break;
-            case 23: launchSlab<T, WIDE, 1, IS_HELL, 4, 2, true>(stream, a, nt); break;
-            case 24: launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 4, 2, true>(stream, a, nt); break;
-            case 19: launchSlab<T, WIDE, 1, IS_HELL, 8, true, true, 1>(stream, a, nt); break; /* 17 + nt x gathers */
-            case 20: launchSlab<T, WIDE, 1, IS_HELL, 8, true, true, 2>(stream, a, nt); break; /* 17 + sc1 x gathers */
-#endif
-            case 22:
-                if (tiled || autoTile)
-                    launchTiled<T, WIDE, IS_HELL, false>(stream, a, tune->xTileShape);
-                else {
-                    if (nt)
-                        findFrozenSlab(handle, stream, a, (kWave / (2 * WIDE)) * WIDE);
-                    if (a.planPacked && strips)
-                        launchSlabPacked<T, WIDE, 2 * WIDE, IS_HELL, 2, true>(stream, a);
-                    else if (a.planPacked)
-                        launchSlabPacked<T, WIDE, 2 * WIDE, IS_HELL, 2, false>(stream, a);
-                    else if (strips)
-                        launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 2, 2, true, 0, true>(stream, a, nt);
-                    else
-                        launchSlab<T, WIDE, 2 * WIDE, IS_HELL, 2, 2, true>(stream, a, nt);
-                }
-                break;
-            default: /* 21 */
-                if (tiled || autoTile)
-                    launchTiled<T, WIDE, IS_HELL, false>(stream, a, tune->xTileShape);
-                else if (a.avgNnzPerRow > 0 && a.avgNnzPerRow <= 8 && form == SPGPU_SPMV_FORM_AUTO && (IS_HELL || a.maxNnz <= 16)) {
-                    /* the caller says the rows are short (avgNnzPerRow: the reference's own tuning hint, which picks its
-                     * threads-per-row shape, hell_spmv_base_template.cuh:306-325): such a row is one stage, and a kernel
-                     * without the prefetch ring needs a third of the registers -- all wavefronts of a 1 M-row system are
-                     * resident at once instead of queueing in three rounds (19.4 -> 17.4 us on configs[0]).  Same order of
-                     * additions (the tail switch is considered every 8 columns, as in the default kernel:
-                     * tests/test_gpu_spmv.py::test_short_row_hint_same_bits pins that on rows of 0 .. 300 entries).  ELL says how long
-                     * its longest row is: beyond two stages the prefetching kernel stays, whatever the average; HELL has only the hint. */
-                    spgpuNoteSpmvForm(handle, SPGPU_SPMV_FORM_GATHER);
-                    a.feedback = nullptr;
-                    launchLean<T, WIDE, IS_HELL>(stream, a);
-                } else {
-                    if (nt)
-                        findFrozenSlab(handle, stream, a, kWave * WIDE);
-                    if (a.planPacked && strips)
-                        launchSlabPacked<T, WIDE, 1, IS_HELL, 8, true>(stream, a);
-                    else if (a.planPacked)
-                        launchSlabPacked<T, WIDE, 1, IS_HELL, 8, false>(stream, a);
-                    else if (strips)
-                        launchSlab<T, WIDE, 1, IS_HELL, 8, 2, true, 0, true>(stream, a, nt);
-                    else
-                        launchSlab<T, WIDE, 1, IS_HELL, 8, 2, true>(stream, a, nt);
-                }
-                break;
+            if (tiled || autoTile) {
+                launchTiled<T, WIDE, IS_HELL>(stream, a);
+            } else if (!PHASED && a.avgNnzPerRow > 0 && a.avgNnzPerRow <= 8 && form == SPGPU_SPMV_FORM_AUTO && (IS_HELL || a.maxNnz <= 16)) {
+                /* the caller says the rows are short (avgNnzPerRow: the reference's own tuning hint, which picks its
+                 * threads-per-row shape, hell_spmv_base_template.cuh:306-325): such a row is one stage, and a kernel
+                 * without the prefetch ring needs a third of the registers -- all wavefronts of a 1 M-row system are
+                 * resident at once instead of queueing in three rounds (19.4 -> 17.4 us on configs[0]).  Same order of
+                 * additions (the tail switch is considered every 8 columns, as in the default kernel:
+                 * tests/test_gpu_spmv.py::test_short_row_hint_same_bits pins that on rows of 0 .. 300 entries).  ELL says how long
+                 * its longest row is: beyond two stages the prefetching kernel stays, whatever the average; HELL has only the hint. */
+                spgpuNoteSpmvForm(handle, SPGPU_SPMV_FORM_GATHER);
+                a.feedback = nullptr;
+                launchLean<T, WIDE, IS_HELL>(stream, a);
+            } else {
+                if (nt)
+                    findFrozenSlab(handle, stream, a, WIDE_GROUP_ROWS);
+                constexpr int PH = PHASED ? 2 * WIDE : 1, UNROLL = PHASED ? 2 : 8;
+                if (a.planPacked && strips)
+                    launchSlabPacked<T, WIDE, PH, IS_HELL, UNROLL, true>(stream, a);
+                else if (a.planPacked)
+                    launchSlabPacked<T, WIDE, PH, IS_HELL, UNROLL, false>(stream, a);
+                else if (strips)
+                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true, true>(stream, a, nt);
+                else
+                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true>(stream, a, nt);
             }
             return;
         }
     }
     a.wideIO = 1; /* RPL == 1: element access is always aligned */
-    switch (variant) {
-#ifdef SPGPU_TUNING_VARIANTS
-    case 3: launchSlab<T, 1, 2, IS_HELL, 4>(stream, a, nt); break;
-    case 4: launchSlab<T, 1, 1, IS_HELL, 4>(stream, a, nt); break;
-    case 14: launchSlab<T, 1, 1, IS_HELL, 8, true>(stream, a, nt); break;
-    case 15: launchSlab<T, 1, 2, IS_HELL, 8>(stream, a, nt); break;
-    case 16: launchSlab<T, 1, 4, IS_HELL, 2, true>(stream, a, nt); break;
-#endif
-    default: /* 13 */
-        if (tiled)
-            launchTiled<T, 1, IS_HELL, false>(stream, a, tune->xTileShape);
-        else
-            launchSlab<T, 1, 2, IS_HELL, 4, 2>(stream, a, nt);
-        break;
-    }
+    if (tiled)
+        launchTiled<T, 1, IS_HELL>(stream, a);
+    else
+        launchSlab<T, 1, 2, IS_HELL, 4, false>(stream, a, nt);
 }
 
 template <typename T, typename ApiT>
@@ -2057,13 +1862,10 @@ using namespace spgpu;
 
 extern "C" {
 
+/* Kept for callers that ask (the test suite's conftest): the lab build of non-default kernel shapes is retired, so always 0. */
 int spgpuTuningVariantsBuilt(void)
 {
-#ifdef SPGPU_TUNING_VARIANTS
-    return 1;
-#else
     return 0;
-#endif
 }
 
 int spgpuHellSpmvForm(spgpuHandle_t handle, spgpuType_t type, const int* rP, int hackSize, const int* hackOffsets, const int* rS, int rows,

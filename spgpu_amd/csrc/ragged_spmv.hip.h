@@ -19,7 +19,7 @@
  *   - the slice of x the workgroup's rows touch is staged in LDS (as in the x-tile form of slabSpmvKernel); entries
  *     outside it are gathered from global memory.
  *   - sub-groups deeper than deepCap keep their first deepCap columns here and hand the rest to the deep kernels
- *     through the handle's deep list (see slabSpmvKernel, DEEP).
+ *     through the handle's deep list (deepRegister; deepItemsKernel and deepFinishKernel in ellpack_spmv.hip).
  *
  * Algorithmic bytes as for slabSpmvKernel, plus 4 per row for rIdx.
  */
@@ -725,7 +725,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
 #ifndef SPGPU_RAGGED_UNROLL
 #define SPGPU_RAGGED_UNROLL(RPL) ((RPL) >= 4 ? 2 : 3) /* wave-wide loads per stage; 3 keeps the 8-byte kernels at 112 VGPRs (4 wavefronts per SIMD: two 8-wavefront workgroups per CU) with two stages in flight */
 #endif
-/* Shapes (SPGPU_RAGGED_SHAPE; 0 is the default): workgroup lanes / tile / sub-groups per workgroup. */
+/* Shapes (SPGPU_RAGGED_SHAPE; 0 is the default, 4 and 5 the staged ones): workgroup lanes / tile / sub-groups per workgroup. */
 /* Returns true if the deep kernels have to follow (false: the launch runs the deep list's items itself). */
 /* Columns per chunk of a split sub-group (raggedSpmvKernel, SPLIT): about 96 (8 stages of the 8-byte kernels), and large
  * enough that the chunk sums of a workgroup whose sub-groups are ALL deepCap deep -- the hacks of set-aside long rows -- fit
@@ -748,35 +748,30 @@ static bool launchRagged(hipStream_t stream, const SlabArgs<T>& in, int shape, b
     SlabArgs<T> a = in;
     a.split = raggedSplit<T>(a.deepCap, (kWave / (32 / RPL)) * UNROLL, spgpuTuning()->raggedSplit);
     const long long subs = ((long long)a.rows + 31) / 32;
-#define SPGPU_RAGGED(WAVES, TILE, SUBS)                                                                               \
+#define LAUNCH_RAGGED(WAVES, TILE, SUBS)                                                                              \
     hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL, WAVES, TILE, SUBS, DEEP>),                          \
                        dim3((unsigned)((subs + (SUBS) - 1) / (SUBS))), dim3((WAVES) * kWave), 0, stream, a)
-#define SPGPU_RAGGED_Z(WAVES, TILE, SUBS, ZB)                                                                         \
+#define LAUNCH_RAGGED_Z(WAVES, TILE, SUBS, ZB)                                                                        \
     hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL, WAVES, TILE, SUBS, DEEP, ZB>),                      \
                        dim3((unsigned)((subs + (SUBS) - 1) / (SUBS))), dim3((WAVES) * kWave), 0, stream, a)
     if (!tiled) {
-        SPGPU_RAGGED(4, 0, 16);
+        LAUNCH_RAGGED(4, 0, 16);
         return true;
     }
     switch (shape) {
-#ifdef SPGPU_TUNING_VARIANTS
-    case 1: SPGPU_RAGGED(8, 65536, 64); break;
-    case 2: SPGPU_RAGGED(4, 49152, 32); break;
-    case 3: SPGPU_RAGGED(4, 32768, 16); break;
-#endif
     case 4: /* 2 048 rows per workgroup, results staged by destination */
     case 5: /* 1 024 rows, staged */
         if constexpr (sizeof(T) <= 8) { /* (16-byte elements: tile + staging leave room for one workgroup per CU -- the default shape) */
             if (shape == 4)
-                SPGPU_RAGGED_Z(8, 49152, 64, 17408);
+                LAUNCH_RAGGED_Z(8, 49152, 64, 17408);
             else
-                SPGPU_RAGGED_Z(8, 49152, 32, 17408);
+                LAUNCH_RAGGED_Z(8, 49152, 32, 17408);
             break;
         }
         [[fallthrough]];
-    default: SPGPU_RAGGED(8, 65536, 32); break;
+    default: LAUNCH_RAGGED(8, 65536, 32); break;
     }
     return true;
-#undef SPGPU_RAGGED
-#undef SPGPU_RAGGED_Z
+#undef LAUNCH_RAGGED
+#undef LAUNCH_RAGGED_Z
 }

@@ -64,27 +64,6 @@ constexpr int kTailLanes = 16; /* switch to whole-wave row processing when <= th
                                   (measured flat between 4 and 16 for the 1-phase kernel, worse above) */
 constexpr int kTailUnroll = 4; /* entries per lane in flight in tail mode */
 
-/* Cache policy of the x gathers (experiments, -DSPGPU_TUNING_VARIANTS): 0 default, 1 non-temporal,
- * 2 agent-scope (sc1: bypasses the per-CU L1). */
-template <int POLICY, typename T> __device__ inline T loadX(const T* p)
-{
-    if constexpr (POLICY == 1) {
-        using Raw = typename RawBits<sizeof(T)>::type;
-        Raw raw = __builtin_nontemporal_load(reinterpret_cast<const Raw*>(p));
-        T out;
-        __builtin_memcpy(&out, &raw, sizeof(T));
-        return out;
-    } else if constexpr (POLICY == 2 && sizeof(T) == 8) {
-        unsigned long long raw = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
-        T out;
-        __builtin_memcpy(&out, &raw, sizeof(T));
-        return out;
-    } else {
-        return *p;
-    }
-}
-
 /* One lane registers a 32-row sub-group deeper than deepCap in the handle's deep list: an entry, and one item per
  * deepChunk columns beyond the cap.  Returns the entry, or -1 when the list is full -- the sub-group then stays with
  * the main kernel.  (The list is global: which entry a sub-group gets depends on scheduling, its sum does not.) */

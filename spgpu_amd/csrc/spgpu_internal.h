@@ -232,7 +232,6 @@ static inline int spgpuFeedbackSaid(int word, int tag)
 
 /* Environment knobs (include/spgpu/tuning.h), read once and cached: no getenv in a launch path. */
 typedef struct SpgpuTuning {
-    int spmvVariant; /* 0 */
     int ntLoads;     /* 1 */
     int tailLanes;   /* -1: kernel default */
     int hdiaVariant; /* 0 */
@@ -247,14 +246,10 @@ typedef struct SpgpuTuning {
     int poisonScratch; /* 0; SPGPU_POISON_SCRATCH=1 (testing): device scratch the library allocates and does not have to initialise -- the deep lists'
                         * sums, a plan's tables, the reduction scratch -- is filled with 0xFF bytes (NaN / -1) when it is allocated: a kernel that
                         * read such a word before writing it would show */
-    int slide;       /* 0; lab builds: 1 = the moving x tile of slide_spmv.hip.h for 8-byte elements (experiment) */
-    int xTileShape;  /* 0 */
     int deepSplit;   /* -1: when rIdx is given */
     int deepCap;     /* 256 */
     int deepKeep;    /* 64: columns of a sub-group deeper than deepCap that stay in the main kernel (-1 or >= deepCap: deepCap) */
-    int ragged;      /* 1: the queue-driven kernel where the deep split is on */
     int raggedShape; /* 0 */
-    int pipeGroups;  /* 0: one workgroup per CU (tests: fewer, so that small matrices run several blocks per workgroup) */
     int raggedSplit; /* -1: about 96 columns per chunk; 0: sub-groups are never cut; > 0: columns per chunk (rounded up to what LDS can park) */
     int l1Nt;        /* -1: by size */
     int plan;        /* 1: ordered matrices get a per-matrix plan (planned_spmv.hip); 0: never */

@@ -465,9 +465,10 @@ def ragged_split(letter, step, deep_cap, asked=-1):
     return max(want, need)
 
 
-def slab_shape(letter, form="gather", tile_shape=0, deep_cap=0, split=-1, deep_keep=None):
+def slab_shape(letter, form="gather", deep_cap=0, split=-1, deep_keep=None):
     """spmv_tail parameters of the kernel the library runs for (type, x form, deep split): csrc/ellpack_spmv.hip
-    launchSlabFamily / launchTiled.  None for the shapes without a tail (complex fp64 outside the deep split: 2 phases)."""
+    launchSlabFamily / launchTiled, and with a deep cap the queue kernel (form "ragged").  None for the shapes without a
+    tail (complex fp64 outside the deep split: 2 phases)."""
     rpl = {"S": 4, "D": 2, "C": 2, "Z": 1}[letter]
     import os
     if deep_keep is None:   # what the library reads (SPGPU_DEEP_KEEP, csrc/core.c), clamped to the cap as it does
@@ -483,16 +484,7 @@ def slab_shape(letter, form="gather", tile_shape=0, deep_cap=0, split=-1, deep_k
         step = phases * (2 if rpl >= 4 else 3)
         return dict(group_rows=32, rows_per_lane=rpl, step=step, tail_lanes=0, phases=phases,
                     main_chunk=ragged_split(letter, step, deep_cap, split), **deep)
-    if form == "xtile":
-        if tile_shape == 1 and not deep:
-            return dict(group_rows=32, rows_per_lane=rpl, step=4 * rpl, tail_lanes=16, phases=2 * rpl) if rpl > 1 else None
-        if letter == "Z" and not deep:
-            return None
-        if tile_shape == 0 and not deep:      # the default tile shape adds in the order of the type's gather kernel
-            return dict(TAIL_SHAPE[letter])
-        return dict(group_rows=64 * rpl, rows_per_lane=rpl, step=4, tail_lanes=16, phases=1, **deep)
-    if deep:   # a lane walks whole rows: 8 columns per stage for 8-byte elements, 4 otherwise
-        return dict(group_rows=64 * rpl, rows_per_lane=rpl, step=8 if letter in "DC" else 4, tail_lanes=16, phases=1, **deep)
+    # gather, strips and the x tile add in the order of the type's gather kernel
     return dict(TAIL_SHAPE[letter]) if letter in TAIL_SHAPE else None
 
 

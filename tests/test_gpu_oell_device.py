@@ -129,60 +129,6 @@ def test_coo_route_builds_the_ordered_hell(gpu, window, long_rows, base):
     assert h["rP"][:h["slots"]].cpu().numpy().tobytes() == hell["indices"].tobytes()
 
 
-def tile_shape(letter, shape, deep=True):
-    """spmv_tail parameters of the x-tile kernels; with a row order the deep split is on (cap 128)."""
-    return O.slab_shape(letter, "xtile", shape, deep_cap=O.DEEP_CAP if deep else 0)
-
-
-@pytest.mark.skipif("not config._lab_build", reason="non-default kernel shape: -DSPGPU_TUNING_VARIANTS build")     # SPGPU_RAGGED=0: the deep split with fixed rows per wavefront
-@pytest.mark.parametrize("shape", [0, 1, 2, 3])
-@pytest.mark.parametrize("letter", ["S", "D"])
-@pytest.mark.parametrize("window,long_rows,pattern", [(512, 40, "near"), (0, 0, "near"), (1024, 0, "random")])
-def test_tile_form_through_ridx_bit_exact(gpu, tuning, letter, shape, window, long_rows, pattern):
-    """Ordered ragged matrix + rIdx, x-tile form: equals the oracle in the kernel's order bit for bit (columns inside the
-    tile come from LDS, the others from global memory -- "random" and the global sort exercise the mix), beta != 0 and
-    in-place included; and equals the SAME product computed from the unordered matrix within the north_star bound."""
-    import torch
-    from spgpu_amd import capi, formats, synth
-    tuning(SPGPU_X_TILE_SHAPE=shape, SPGPU_RAGGED=0)
-    n = 6000 + 13
-    h, (r, c, v), lengths = _ordered_case(gpu, n, letter, window, long_rows, pattern=pattern)
-    sub = dict(letter=letter, rows=n, values=h["cM"][:h["slots"]].cpu().numpy(), indices=h["rP"][:h["slots"]].cpu().numpy(),
-               hack_offsets=h["hack_offsets"].cpu().numpy(), hack_size=32, row_lengths=h["rS"][:n].cpu().numpy(), base=0)
-    r_idx = h["rIdx"].cpu().numpy()
-    x = synth.values_for(letter, 11, n)
-    y = synth.values_for(letter, 12, n)
-    dx, dy = formats.to_device(x), formats.to_device(y)
-    capi.spgpuSetSpmvForm(gpu, capi.FORM_XTILE)
-    try:
-        for alpha, beta, in_place in ((1.0, 0.0, False), (-0.75, 0.5, False), (2.0, 1.0, True)):
-            dz = dy.clone() if in_place else torch.full((n,), float("nan"), dtype=dx.dtype, device="cuda")
-            capi.hellspmv[letter](gpu, _dp(dz), _dp(dz if in_place else (dy if beta != 0 else None)), capi.scalar(letter, alpha),
-                                  _dp(h["cM"]), _dp(h["rP"]), 32, _dp(h["hack_offsets"]), _dp(h["rS"]), _dp(h["rIdx"]), 12, n,
-                                  _dp(dx), capi.scalar(letter, beta), 0)
-            torch.cuda.synchronize()
-            got = dz.cpu().numpy()
-            want = O.spmv_tail(sub, x, y if beta != 0 else None, alpha, beta, r_idx=r_idx, **tile_shape(letter, shape))
-            assert got.tobytes() == want.tobytes(), (alpha, beta, in_place)
-    finally:
-        capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
-    # independent of any summation order: alpha*A*x from the ORIGINAL triplets in extended precision
-    exact = np.zeros(n, np.longdouble)
-    scale = np.zeros(n, np.longdouble)
-    np.add.at(exact, r, v.astype(np.longdouble) * x[c].astype(np.longdouble))
-    np.add.at(scale, r, np.abs(v.astype(np.longdouble) * x[c].astype(np.longdouble)))
-    dz = torch.empty(n, dtype=dx.dtype, device="cuda")
-    capi.spgpuSetSpmvForm(gpu, capi.FORM_XTILE)
-    try:
-        capi.hellspmv[letter](gpu, _dp(dz), None, capi.scalar(letter, 1.0), _dp(h["cM"]), _dp(h["rP"]), 32, _dp(h["hack_offsets"]),
-                              _dp(h["rS"]), _dp(h["rIdx"]), 12, n, _dp(dx), capi.scalar(letter, 0.0), 0)
-        torch.cuda.synchronize()
-    finally:
-        capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
-    tol = {"S": 1e-4, "D": 1e-6}[letter]
-    assert np.all(np.abs(dz.cpu().numpy().astype(np.longdouble) - exact) <= tol * scale + np.finfo(np.float64).tiny)
-
-
 @pytest.mark.parametrize("name", sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*.npz"))
                                         if os.path.basename(p)[:-4] not in ("empty_d", "onerow_z")))
 @pytest.mark.parametrize("form", ["gather", "strips", "xtile"])
@@ -206,7 +152,7 @@ def test_every_form_on_the_fixtures(gpu, name, form):
                 assert z.tobytes() == O.default_spmv(hell if isinstance(mat, formats.DeviceHell) else ell, g["x"], y, alpha, beta).tobytes()
             elif form == "xtile" and letter != "Z" and not (isinstance(mat, formats.DeviceEll) and mat.rS is None):
                 want = O.spmv_tail(hell if isinstance(mat, formats.DeviceHell) else ell, g["x"], y, alpha, beta,
-                                   **tile_shape(letter, 0, deep=False))
+                                   **O.slab_shape(letter, "xtile"))
                 assert z.tobytes() == want.tobytes()
     finally:
         capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
@@ -230,33 +176,6 @@ def test_one_column_matrix_strips_form(gpu):
     finally:
         capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
     assert z.tobytes() == (v * 3.0).tobytes()
-
-
-@pytest.mark.skipif("not config._lab_build", reason="non-default kernel shape: -DSPGPU_TUNING_VARIANTS build")     # SPGPU_RAGGED=0
-@pytest.mark.parametrize("cap", [16, 128])
-@pytest.mark.parametrize("form", ["gather", "xtile"])
-@pytest.mark.parametrize("name", ["powerlaw_s_b1_h64", "powerlaw_d_b0_h32", "powerlaw_c_b0_h32", "powerlaw_z_b1_h64"])
-def test_deep_split_every_type_bit_exact(gpu, tuning, name, form, cap):
-    """The deep split on its own (SPGPU_DEEP_SPLIT=1, no row order): sub-groups deeper than the cap are finished by
-    deepSpmvKernel; HELL and ELL, all four types, hack 32 and 64, base 0 and 1, beta == 0 and != 0, against the oracle's
-    restatement of that order bit for bit and against the extended-precision fixtures."""
-    from spgpu_amd import capi, formats
-    from test_gpu_spmv import _load, _mats, _run, _within
-    tuning(SPGPU_DEEP_SPLIT=1, SPGPU_DEEP_CAP=cap, SPGPU_RAGGED=0)
-    g = _load(name)
-    letter, ell, hell, _ = _mats(g)
-    shape = O.slab_shape(letter, form, 0, deep_cap=cap)
-    capi.spgpuSetSpmvForm(gpu, capi.FORM_XTILE if form == "xtile" else capi.FORM_GATHER)
-    try:
-        for beta in (0.0, g["beta"][()] if g["beta"][()] != 0 else 0.5):
-            y = g["y"] if beta != 0 else None
-            for mat, host in ((formats.DeviceHell(hell), hell), (formats.DeviceEll(ell), ell)):
-                z = _run(gpu, mat, g["x"], y, g["alpha"][()], beta)
-                assert z.tobytes() == O.spmv_tail(host, g["x"], y, g["alpha"][()], beta, **shape).tobytes()
-                if beta == g["beta"][()]:
-                    assert _within(z, g, letter) <= 1.0
-    finally:
-        capi.spgpuSetSpmvForm(gpu, capi.FORM_AUTO)
 
 
 def test_deep_queue_overflow_stays_correct(gpu, tuning):
@@ -289,7 +208,7 @@ def test_deep_queue_overflow_stays_correct(gpu, tuning):
     assert capi.spgpuDeepListOverflows(gpu) == before + 2
 
 
-@pytest.mark.parametrize("shape,form", [(0, "auto"), (0, "gather"), (4, "auto"), (5, "auto")] + [pytest.param(k, "auto", marks=pytest.mark.skipif("not config._lab_build", reason="non-default kernel shape: -DSPGPU_TUNING_VARIANTS build")) for k in (1, 2, 3)])
+@pytest.mark.parametrize("shape,form", [(0, "auto"), (0, "gather"), (4, "auto"), (5, "auto")])
 @pytest.mark.parametrize("letter", ["S", "D", "C", "Z"])
 @pytest.mark.parametrize("window,long_rows,pattern,hack", [(512, 40, "near", 32), (0, 0, "near", 64), (1024, 0, "random", 32), (256, 100, "near", 96)])
 def test_ragged_kernel_through_ridx_bit_exact(gpu, tuning, letter, shape, form, window, long_rows, pattern, hack):

@@ -18,9 +18,6 @@ pytestmark = pytest.mark.gpu
 
 TOL = {"S": 1e-4, "C": 1e-4, "D": 1e-6, "Z": 1e-6}
 # default dispatch of ellpack_spmv.hip (launchSlabFamily): see oracle_api.default_spmv
-_ONE, _TWO = dict.fromkeys("SDCZ", 1), dict.fromkeys("SDCZ", 2)
-_PHX2 = {"S": 8, "D": 4, "C": 4, "Z": 2}       # wide kernel with 2*RPL phases (Z has RPL 1: narrow, 2 phases)
-VARIANT_PHASES = {1: _PHX2, 2: {**_ONE, "Z": 2}, 3: _TWO, 4: _ONE, 6: _PHX2, 12: {**_ONE, "Z": 2}, 13: _TWO}
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*.npz")))
 
@@ -92,26 +89,13 @@ def test_fixture_parity_all_formats(gpu, name):
         assert z.tobytes() == O.hdia_spmv(hdia, g["x"], y, alpha, beta).tobytes()
 
 
-@pytest.mark.parametrize("variant", [0] + [pytest.param(v, marks=pytest.mark.skipif("not config._lab_build", reason="a forced kernel shape: -DSPGPU_TUNING_VARIANTS build"))
-                                           for v in (1, 2, 3, 4, 6, 12, 13, 17, 18, 21, 22)])
+@pytest.mark.parametrize("variant", [0])     # the kernel shape the library picks for the type (the forced shapes of the retired lab build are gone)
 @pytest.mark.parametrize("name", ["powerlaw_s_b1_h64", "powerlaw_d_b0_h32", "powerlaw_c_b0_h32", "powerlaw_z_b1_h64"])
-def test_every_kernel_variant_bit_exact(gpu, name, variant, tuning):
+def test_every_kernel_variant_bit_exact(gpu, name, variant):
     from spgpu_amd import formats
-    tuning(SPGPU_SPMV_VARIANT=variant)
     g = _load(name)
     letter, ell, hell, _ = _mats(g)
-    # Z (16-byte elements) has no wide form: wide requests run narrow 2x4 pipe
-    rpl = 16 // np.dtype(O.NP_DTYPE[letter]).itemsize
-    if variant == 0:          # what the library picks for the type (the only shapes of the product build)
-        want_of = lambda m, yy, b: O.default_spmv(m, g["x"], yy, g["alpha"][()], b)
-    elif variant in (17, 18, 21, 22) and letter != "Z":
-        one_phase = variant in (17, 21)
-        ph = 1 if one_phase else 2 * rpl                         # 18/22: wide kernel with 2*RPL phases x 2 columns
-        shape = dict(group_rows=(64 // ph) * rpl, rows_per_lane=rpl, step=8 if one_phase else 2 * ph, tail_lanes=16, phases=ph)
-        want_of = lambda m, yy, b: O.spmv_tail(m, g["x"], yy, g["alpha"][()], b, **shape)
-    else:
-        ph = 2 if (variant in (17, 18, 21, 22) and letter == "Z") else VARIANT_PHASES[variant][letter]
-        want_of = lambda m, yy, b: (O.hell_spmv if "hack_offsets" in m else O.ell_spmv)(m, g["x"], yy, g["alpha"][()], b, phases=ph)
+    want_of = lambda m, yy, b: O.default_spmv(m, g["x"], yy, g["alpha"][()], b)
     for beta in (0.0, g["beta"][()] if g["beta"][()] != 0 else 0.5):
         y = g["y"] if beta != 0 else None
         z = _run(gpu, formats.DeviceHell(hell), g["x"], y, g["alpha"][()], beta)

@@ -5,7 +5,7 @@ length (spgpuOellOrderDevice).  Every timing is followed by an oracle check of t
 
     python tools/exp_tile.py [D|S] [rows] [cases: uniform,mild,powerlaw]
 
-Environment: EXP_FORMS = comma list of  auto | gather | strips | tileN (x-tile shape N) | raggedN (the kernel for ordered
+Environment: EXP_FORMS = comma list of  auto | gather | strips | tile (x tile in LDS) | sweep | raggedN (the kernel for ordered
 rows, workgroup shape N) | raggedg (the same with plain gathers); a suffix xR (ragged0x4) runs it with R consecutive row
 blocks per XCD.  EXP_PATTERNS = near,band,random (power-law) or near2048,near512,window,banded (uniform);
 EXP_ORDERS = window:longRows pairs (2048:256,...); EXP_ONLY_WINDOWED=1 skips the plain and globally sorted layouts;
@@ -39,13 +39,8 @@ one, zero = capi.scalar(letter, 1.0), capi.scalar(letter, 0.0)
 x = synth.device_vector(n, letter, 3)
 z = torch.zeros(n, dtype=x.dtype, device="cuda:0")
 xs = x.cpu().numpy()
-FORMS = {"auto": 0, "gather": 1, "strips": 2, "tile0": 3, "tile1": 3, "tile2": 3, "tile3": 3, "sweep": 4}
+FORMS = {"auto": 0, "gather": 1, "strips": 2, "tile": 3, "sweep": 4}
 DEEP_CAP = int(os.environ.get("SPGPU_DEEP_CAP", "256"))
-
-
-def spgpu_lab():
-    """a -DSPGPU_TUNING_VARIANTS build keeps the older kernels for ordered rows selectable (SPGPU_RAGGED=0)"""
-    return bool(capi.spgpuTuningVariantsBuilt()) and os.environ.get("SPGPU_RAGGED", "1") == "0"
 
 
 def shape_of(form, ordered):
@@ -53,13 +48,9 @@ def shape_of(form, ordered):
     deep = DEEP_CAP if (ordered and os.environ.get("SPGPU_DEEP_SPLIT", "-1") != "0") or os.environ.get("SPGPU_DEEP_SPLIT") == "1" else 0
     if form == "sweep":
         return dict(group_rows=64, rows_per_lane=1, step=1, tail_lanes=0, phases=1)      # ascending k, nothing else
-    if form.startswith(("share", "pipe")):
-        return O.slab_shape(letter, "share")
-    if form.startswith("ragged") or (form in ("auto", "gather") and ordered and not spgpu_lab()):     # with a row order the product runs the queue kernel in every form
-        return O.slab_shape(letter, "ragged", 0, deep_cap=deep, split=int(os.environ.get("SPGPU_RAGGED_SPLIT", "-1")))
-    if form.startswith("tile"):
-        return O.slab_shape(letter, "xtile", int(form[4:]), deep_cap=deep)
-    return O.slab_shape(letter, "gather", 0, deep_cap=deep)
+    if form.startswith("ragged") or deep:     # with the deep split (a row order) the library runs the queue kernel in every form
+        return O.slab_shape(letter, "ragged", deep_cap=deep, split=int(os.environ.get("SPGPU_RAGGED_SPLIT", "-1")))
+    return O.slab_shape(letter, "xtile" if form == "tile" else "gather")
 
 
 def check(h, form, windows=3, rows=2048):
@@ -104,11 +95,9 @@ def run(h, label, forms):
         os.environ["SPGPU_RAGGED_SPLIT"] = split or "-1"
         form, _, xcd = full.partition("x")          # "ragged0x4": shape 0 with runs of 4 row blocks per XCD
         os.environ["SPGPU_XCD_ORDER"] = xcd or os.environ.get("EXP_XCD_ORDER", "0")
-        os.environ["SPGPU_X_TILE_SHAPE"] = form[4:] if form.startswith("tile") else "0"
-        os.environ["SPGPU_RAGGED"] = "3" if form.startswith("pipe") else "2" if form.startswith("share") else "1" if form.startswith("ragged") else "0"      # raggedN / shareN: shape N with the tile; raggedg / shareg: gathers
-        os.environ["SPGPU_RAGGED_SHAPE"] = form[6:] if form.startswith("ragged") and form[6:].isdigit() else form[5:] if form.startswith("share") and form[5:].isdigit() else form[4:] if form.startswith("pipe") and form[4:].isdigit() else "0"
+        os.environ["SPGPU_RAGGED_SHAPE"] = form[6:] if form.startswith("ragged") and form[6:].isdigit() else "0"      # raggedN: shape N with the tile; raggedg: gathers
         capi.spgpuTuningReload()
-        capi.spgpuSetSpmvForm(handle, 1 if form in ("raggedg", "shareg", "pipeg") else 0 if form.startswith(("ragged", "share", "pipe")) else 3 if form.startswith("tile") else FORMS[form])
+        capi.spgpuSetSpmvForm(handle, 1 if form == "raggedg" else 0 if form.startswith("ragged") else FORMS[form])
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(stream):
             for _ in range(3):
@@ -170,7 +159,7 @@ if "uniform" in cases:
         h = synth.hell_uniform_on_device(n // 32 * 32, 32, pattern, letter, 32, seed=1)
         h["slots"] = h["nnz"]
         torch.cuda.synchronize()
-        run(h, f"uniform 32/row, columns {pattern}", os.environ.get("EXP_FORMS", "gather,strips,tile0,tile2,tile3,tile4,tile5").split(","))
+        run(h, f"uniform 32/row, columns {pattern}", os.environ.get("EXP_FORMS", "gather,strips,tile").split(","))
         del h
         torch.cuda.empty_cache()
 
@@ -184,7 +173,7 @@ if "mild" in cases:
     torch.cuda.synchronize()
     for name, order in ([] if os.environ.get("EXP_ONLY_WINDOWED") else [("plain", None)]) + [(f"sorted window {w}", (w, 0)) for w in (int(v) for v in os.environ.get("EXP_MILD_WINDOWS", "1024,2048,4096").split(","))]:
         h = formats.coo_to_ordered_hell_device(handle, n, rows_t, cols_t, vals_t, letter, 32, *(order or (0, 0)), order=order is not None)
-        run(h, f"24..40/row {mild_pattern}, {name}", os.environ.get("EXP_FORMS", "gather,tile0,tile2,tile3").split(","))
+        run(h, f"24..40/row {mild_pattern}, {name}", os.environ.get("EXP_FORMS", "gather,tile").split(","))
         del h
         torch.cuda.empty_cache()
     del rows_t, cols_t, vals_t
@@ -233,7 +222,7 @@ if "powerlaw" in cases:
                                                    order=order is not None, aligned=aligned)
             if aligned and os.environ.get("EXP_ALIGNED") == "check":    # the device order against this file's numpy statement of it
                 assert h["rIdx"].cpu().numpy().tolist() == aligned_order(lengths, *order).tolist()
-            forms = os.environ.get("EXP_GLOBAL_FORMS", "gather").split(",") if ((pattern == "random" and not os.environ.get("EXP_WINDOWS_FOR_ALL")) or order is None or order == (0, 0)) else os.environ.get("EXP_FORMS", "gather,tile0,tile2,tile3").split(",")
+            forms = os.environ.get("EXP_GLOBAL_FORMS", "gather").split(",") if ((pattern == "random" and not os.environ.get("EXP_WINDOWS_FOR_ALL")) or order is None or order == (0, 0)) else os.environ.get("EXP_FORMS", "gather,tile").split(",")
             run(h, f"power-law {pattern}, {name}", forms)
             del h
             torch.cuda.empty_cache()

@@ -21,8 +21,8 @@ os.makedirs(out, exist_ok=True)
 bench = [os.path.join(ROOT, "bench.py"), "--full", "--no-extras"] + (["--workload", "spmm"] if kind == "spmm" else []) + (["--frozen"] if kind == "spmv_frozen" else [])
 # spmv_frozen: the headline matrix after spgpuHellSpmvFreeze (bench.py --frozen): the PACKED instantiation of the same kernel
 kernel_key = ("hellSpmmStripKernel" if kind == "spmm" else
-              "slabSpmvKernel<double, 2, 1, true, true, 8, 2, true, 0, true, 256, 0, false, 1, 0, true>" if kind == "spmv_frozen" else
-              "slabSpmvKernel<double, 2, 1, true, true, 8, 2, true, 0, true, 256, 0, false, 1, 0, false>")
+              "slabSpmvKernel<double, 2, 1, true, true, 8, true, true, true, 256, 0, 0, true>" if kind == "spmv_frozen" else
+              "slabSpmvKernel<double, 2, 1, true, true, 8, true, true, true, 256, 0, 0, false>")
 env = dict(os.environ, TMPDIR="/tmp")
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box, lab build (SPGPU_LIB=spgpu_amd/lib_lab/libspgpu.so): does any ordered SpMV path read LDS it has not written?
+"""GPU box, debug build (make lib EXTRA_HIPFLAGS=-DSPGPU_DEBUG): does any ordered SpMV path read LDS it has not written?
 spgpuDebugFillLds (csrc/debug_lds.hip) fills every CU's LDS with one word (EXP_LDS_WORD=0 | 0xffffffff) in front of every call; the result must still be the oracle's bytes.
 Paths: the first call (list), the planned call, SPGPU_PLAN=0, a stream without a list (stateless), stale plans (matrices swapped in
 place), all four types, the shapes of tests/test_gpu_plan.py.   python tools/stress_lds.py [matrices]"""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: the scenario of tests/test_gpu_plan.py::test_streams_come_and_go_lists_change_hands many times in one process -- a new
 stream for every ordered SpMV of one matrix -- with, for every call that does not give the oracle's bytes, which rows differ and
-what the handle's counters say.   python tools/stress_streams.py [rounds] ; SPGPU_LIB=... for the lab build"""
+what the handle's counters say.   python tools/stress_streams.py [rounds] ; SPGPU_LIB=... for another build"""
 import ctypes as C
 import os
 import sys
