@@ -4,18 +4,12 @@
  * only compile-time knobs are THREAD_BLOCK / MAX_NNZ_PER_WG in the *_base.cuh
  * files).  The library reads these environment variables ONCE, on the first
  * call that needs them -- never in a launch path -- and again whenever
- * spgpuTuningReload() is called (the A/B tools and the kernel-shape parity
- * tests change them between launches):
+ * spgpuTuningReload() is called (the tests change them between launches).
+ * They reach production paths on small inputs; none selects a kernel shape the default dispatch never takes:
  *
- *   SPGPU_NT_LOADS       0: no non-temporal hint on the coefficient/index streams (default 1)
  *   SPGPU_X_STRIPS       ELL/HELL SpMV: x values of a strip of rows with one 16-byte load where the rows name consecutive
  *                        columns.  Unset: learnt per matrix from the kernel's own feedback (csrc/ellpack_spmv.hip);
  *                        1: the strip-capable kernel always; 0: the gather-only kernel always
- *   SPGPU_TAIL_LANES     busy lanes below which a wavefront switches to whole-wave rows (default 16)
- *   SPGPU_HDIA_VARIANT   2: 8 diagonals per stage instead of 4
- *   SPGPU_HDIA_BLOCK     HDIA workgroup size 256 / 512 (default) / 1024
- *   SPGPU_HDIA_NARROW    1: one row per lane even when 16-byte accesses are possible
- *   SPGPU_XCD_ORDER      HDIA: 0 hardware workgroup order (default), n: XCD-contiguous runs of n
  *   SPGPU_DEEP_CAP       ELL/HELL SpMV with a row order: a 32-row sub-group deeper than this many columns (default 256) hands
  *                        columns to the deep kernels (the deep list below); SPGPU_DEEP_SPLIT=1 / 0 forces that on without a
  *                        row order / off with one
@@ -25,9 +19,8 @@
  *                        each -- lived as long as the whole launch (profiles/r03_ragged_workgroup_trace.txt)
  *   SPGPU_RAGGED_SPLIT   ELL/HELL SpMV with a row order: columns per chunk of a 32-row sub-group that several wavefronts share
  *                        (unset: about 96; 0: never cut; rounded up to what LDS can park; csrc/ragged_spmv.hip.h, SPLIT)
- *   SPGPU_SPMM_VARIANT   SpMM kernel shape (0 = default, see csrc/hell_spmm.hip)
- *   SPGPU_L1_NT          Level-1 streams non-temporal: 1 always, 0 never, unset: vectors beyond the Infinity Cache
- *   SPGPU_L1_BLOCKS      grid cap of the Level-1 kernels (default 16384)
+ *   SPGPU_RAGGED_SHAPE   ELL/HELL SpMV with a row order: unset or 0, a probe picks the workgroup shape per matrix; 4: always the
+ *                        shape of 2 048 rows per workgroup with the results staged by destination (csrc/ragged_spmv.hip.h)
  *   SPGPU_POISON_SCRATCH 1 (testing): device scratch the library allocates without having to initialise it -- the deep lists'
  *                        sums, a plan's tables, the reduction scratch -- is filled with 0xFF bytes (NaN / -1) at allocation, so
  *                        that a kernel reading such a word before writing it shows in the results
@@ -69,13 +62,10 @@ int spgpuDeepListsRecycled(spgpuHandle_t handle);
  * plan that has gone stale (another matrix at the same addresses): a plan decides who computes, never what or in which order.
  * A stale plan is noticed by the kernels and rebuilt by the next call.  Launches captured into a HIP graph never use a plan,
  * unless held (spgpu/ext/graph.h).
+ * A workgroup of deep sub-groups takes a RUN of 8 consecutive ones of the plan's list -- after an ordering these are neighbours in
+ * the matrix (one window of set-aside long rows), so their gathers of x meet in one L2 -- and those workgroups are spread over
+ * the first 60 % of the grid.
  *   SPGPU_PLAN=0                 no plans
- *   SPGPU_PLAN_DEEP_PER_BLOCK    deep sub-groups per workgroup of theirs (default 8, 1 .. 8)
- *   SPGPU_PLAN_DEEP_RUNS         1 (default): such a workgroup takes a RUN of consecutive deep sub-groups of the list -- after an
- *                                ordering these are neighbours in the matrix (one window of set-aside long rows), so their gathers
- *                                of x meet in one L2; 0: every N-th sub-group (the dealing of the first planned kernels)
- *   SPGPU_PLAN_DEEP_SPREAD       those workgroups are spread over the first N per cent of the grid (default 60; 0: all in front;
- *                                -1: all behind the blocks of rows)
  * spgpuSpmvPlanCounts: launches that ran with a plan, analyses started, plans found stale (any pointer may be NULL).
  */
 void spgpuSpmvPlanCounts(spgpuHandle_t handle, int* uses, int* builds, int* stales);
@@ -198,8 +188,8 @@ int spgpuTuningVariantsBuilt(void);
  *           <= 1.5 x its nonzeros) -- and the matrix has 2 Mi rows or more (the form wants a grid that fills the chip).
  *           SPGPU_AUTO_SWEEP=0 keeps AUTO out of it.
  *
- * The hint applies to every later SpMV call on the handle, from any thread; SPGPU_X_STRIPS / SPGPU_X_TILE in the
- * environment override it.
+ * The hint applies to every later SpMV call on the handle, from any thread; SPGPU_X_STRIPS in the environment
+ * overrides it (1: STRIPS, 0: GATHER).
  */
 #define SPGPU_SPMV_FORM_AUTO   0
 #define SPGPU_SPMV_FORM_GATHER 1

@@ -737,16 +737,7 @@ static int envInt(const char* name, int fallback)
 void spgpuTuningReload(void)
 {
     SpgpuTuning t;
-    t.ntLoads = envInt("SPGPU_NT_LOADS", 1);
-    t.tailLanes = envInt("SPGPU_TAIL_LANES", -1);
-    t.hdiaVariant = envInt("SPGPU_HDIA_VARIANT", 0);
-    t.hdiaBlock = envInt("SPGPU_HDIA_BLOCK", 512);
-    t.hdiaNarrow = envInt("SPGPU_HDIA_NARROW", 0);
-    t.xcdOrder = envInt("SPGPU_XCD_ORDER", 0);
-    t.spmmVariant = envInt("SPGPU_SPMM_VARIANT", 0);
-    t.l1Blocks = envInt("SPGPU_L1_BLOCKS", 0);
     t.xStrips = envInt("SPGPU_X_STRIPS", -1);
-    t.xTile = envInt("SPGPU_X_TILE", -1);
     t.autoSweep = envInt("SPGPU_AUTO_SWEEP", 1);
     t.poisonScratch = envInt("SPGPU_POISON_SCRATCH", 0);
     t.deepSplit = envInt("SPGPU_DEEP_SPLIT", -1);
@@ -754,13 +745,8 @@ void spgpuTuningReload(void)
     t.deepKeep = envInt("SPGPU_DEEP_KEEP", 64);
     t.raggedShape = envInt("SPGPU_RAGGED_SHAPE", 0);
     t.raggedSplit = envInt("SPGPU_RAGGED_SPLIT", -1);
-    t.l1Nt = envInt("SPGPU_L1_NT", -1);
     t.plan = envInt("SPGPU_PLAN", 1);
-    t.planDeepSpread = envInt("SPGPU_PLAN_DEEP_SPREAD", 60);
-    t.planDeepPerBlock = envInt("SPGPU_PLAN_DEEP_PER_BLOCK", 8);
-    t.planDeepRuns = envInt("SPGPU_PLAN_DEEP_RUNS", 1);
     t.freezeEscapesPct = envInt("SPGPU_FREEZE_MAX_ESCAPES_PCT", 1);
-    t.stageLate = envInt("SPGPU_STAGE_LATE", 1);
     tuning = t;
     __atomic_store_n(&tuningLoaded, 1, __ATOMIC_RELEASE);
 }

@@ -1096,16 +1096,13 @@ static bool alignedTo(const void* p, size_t bytes)
 
 /* The gather and strip forms (launchSlabFamily): the next stage prefetched behind the current gathers. */
 template <typename T, int RPL, int PH, bool IS_HELL, int UNROLL, bool TAIL, bool STRIPS = false>
-static void launchSlab(hipStream_t stream, const SlabArgs<T>& a, bool nt)
+static void launchSlab(hipStream_t stream, const SlabArgs<T>& a)
 {
     constexpr int GROUP_ROWS = (kWave / PH) * RPL;
     constexpr int WAVES = kBlockThreads / kWave;
     const long long groups = ((long long)a.rows + GROUP_ROWS - 1) / GROUP_ROWS;
     const unsigned blocks = (unsigned)((groups + WAVES - 1) / WAVES);
-    if (nt)
-        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, true, TAIL, STRIPS>), dim3(blocks), dim3(kBlockThreads), 0, stream, a);
-    else
-        hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, false, UNROLL, true, TAIL, STRIPS>), dim3(blocks), dim3(kBlockThreads), 0, stream, a);
+    hipLaunchKernelGGL((slabSpmvKernel<T, RPL, PH, IS_HELL, true, UNROLL, true, TAIL, STRIPS>), dim3(blocks), dim3(kBlockThreads), 0, stream, a);
 }
 
 /* The x-tile forms.  Workgroup size and tile size go together: the tile has to hold the columns of the workgroup's
@@ -1426,24 +1423,21 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
      * next stage prefetched AFTER the current gathers are issued and whole-wave tail rows -- D/C fastest with a lane walking
      * whole rows, 8 slab columns per stage (banded 5.9 TB/s, windowed columns +13 % over prefetch-before); S (PHASED) with
      * 8 phases x 2 columns (5.4-6.0 TB/s).  16-byte elements (Z) and unaligned streams run narrow: RPL = 1 with 2 phases
-     * x 4 columns (5.9 TB/s).  SPGPU_NT_LOADS 0/1: non-temporal hint on the coefficient/index streams (default 1). */
+     * x 4 columns (5.9 TB/s).  The coefficient/index streams carry the non-temporal hint. */
     constexpr bool PHASED = sizeof(T) == 4;
     constexpr int WIDE_GROUP_ROWS = PHASED ? (kWave / (2 * WIDE)) * WIDE : kWave * WIDE; /* rows of a wavefront of the wide kernel */
     const SpgpuTuning* tune = spgpuTuning();
-    a.tailLanes = tune->tailLanes >= 0 ? tune->tailLanes : kTailLanes;
-    const bool nt = tune->ntLoads != 0;
+    a.tailLanes = kTailLanes;
 
     /* Strip x loads (consume<STRIPS>): which form a matrix runs in is learnt from the kernel itself.  The
      * strip-capable kernel's sample wavefronts write "ran as strips / as gathers" into pinned host memory; a
      * later call on the same matrix (same rP, same rows) reads that -- no synchronisation, whatever is there --
      * and takes the gather-only kernel when at least two of the three samples said gathers.  Both kernels are
      * correct for every matrix; a stale or missing answer only costs speed.  SPGPU_X_STRIPS = 0 / 1 fixes the form. */
-    /* How x is fetched (include/spgpu/tuning.h): the handle's hint, overridden by the environment knobs. */
+    /* How x is fetched (include/spgpu/tuning.h): the handle's hint, overridden by SPGPU_X_STRIPS. */
     int form = spgpuGetSpmvForm(handle);
     if (tune->xStrips >= 0)
         form = tune->xStrips ? SPGPU_SPMV_FORM_STRIPS : SPGPU_SPMV_FORM_GATHER;
-    if (tune->xTile >= 0)
-        form = tune->xTile ? SPGPU_SPMV_FORM_XTILE : (form == SPGPU_SPMV_FORM_XTILE ? SPGPU_SPMV_FORM_AUTO : form);
     if (form == SPGPU_SPMV_FORM_SWEEP) {
         /* the caller's choice for scattered columns that ascend inside a row; needs 16-byte slab accesses and no row order */
         if (wideOk && !a.rIdx) {
@@ -1463,8 +1457,6 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
     bool deepSplit = (tune->deepSplit >= 0 ? tune->deepSplit != 0 : a.rIdx != nullptr) && wideOk;
     a.deepCap = tune->deepCap > 0 ? tune->deepCap : 256;
     a.deepKeep = tune->deepKeep >= 0 && tune->deepKeep < a.deepCap ? tune->deepKeep : a.deepCap;
-    a.xcdRun = tune->xcdOrder;
-    a.stageLate = tune->stageLate != 0;
     a.deepChunk = kDeepChunk;
     a.deepHeader = nullptr;
     a.deepEntries = nullptr;
@@ -1516,14 +1508,14 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
          * allocation failed): the same kernel family without any state -- the matrix' plan if it is ready, else no plan at
          * all (every deep sub-group worked off by its own block).  Same bits in every case. */
         const bool tiledForm = form != SPGPU_SPMV_FORM_GATHER;
-        if (noDeepList && !(shape == 4 || shape == 5))
+        if (noDeepList && shape != 4)
             shape = 0;
         if (prepared) {
-            if (!tiledForm || shape == 0 || shape == 4 || shape == 5)
+            if (!tiledForm || shape == 0 || shape == 4)
                 *prepared = launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, false, freeze ? 2 : 1) ? 1 : 0;
             return;
         }
-        if ((!tiledForm || shape == 0 || shape == 4 || shape == 5) && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, noDeepList, 0))
+        if ((!tiledForm || shape == 0 || shape == 4) && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, noDeepList, 0))
             return;
         const bool deepKernels = launchRagged<T, WIDE, IS_HELL, true>(stream, a, shape, form != SPGPU_SPMV_FORM_GATHER);
         if (deepPossible && deepKernels)
@@ -1543,7 +1535,7 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
         /* (the forms below learn what they need from their own launches) -- Freeze of a matrix without a row order: the default
          * kernels' 16-bit index copy */
         if constexpr (WIDE > 1) {
-            if (freeze && !a.rIdx && wideOk && !tiled && nt)
+            if (freeze && !a.rIdx && wideOk && !tiled)
                 *prepared = freezeSlab<T, IS_HELL>(handle, stream, a, WIDE_GROUP_ROWS) ? 1 : 0;
         }
         return;
@@ -1611,17 +1603,16 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
                 a.feedback = nullptr;
                 launchLean<T, WIDE, IS_HELL>(stream, a);
             } else {
-                if (nt)
-                    findFrozenSlab(handle, stream, a, WIDE_GROUP_ROWS);
+                findFrozenSlab(handle, stream, a, WIDE_GROUP_ROWS);
                 constexpr int PH = PHASED ? 2 * WIDE : 1, UNROLL = PHASED ? 2 : 8;
                 if (a.planPacked && strips)
                     launchSlabPacked<T, WIDE, PH, IS_HELL, UNROLL, true>(stream, a);
                 else if (a.planPacked)
                     launchSlabPacked<T, WIDE, PH, IS_HELL, UNROLL, false>(stream, a);
                 else if (strips)
-                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true, true>(stream, a, nt);
+                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true, true>(stream, a);
                 else
-                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true>(stream, a, nt);
+                    launchSlab<T, WIDE, PH, IS_HELL, UNROLL, true>(stream, a);
             }
             return;
         }
@@ -1630,7 +1621,7 @@ static void launchSlabFamily(spgpuHandle_t handle, const SlabArgs<T>& in, int* p
     if (tiled)
         launchTiled<T, 1, IS_HELL>(stream, a);
     else
-        launchSlab<T, 1, 2, IS_HELL, 4, false>(stream, a, nt);
+        launchSlab<T, 1, 2, IS_HELL, 4, false>(stream, a);
 }
 
 template <typename T, typename ApiT>
@@ -1674,7 +1665,7 @@ static void hellSpmv(spgpuHandle_t handle, ApiT* z, const ApiT* y, ApiT alpha, c
     a.planBlocks = nullptr;
     a.planDeepSubs = nullptr;
     a.planFlags = nullptr;
-    a.planDeep = a.planMainBlocks = a.planDeepPerBlock = a.planDeepStride = a.planDeepRuns = 0;
+    a.planDeep = a.planMainBlocks = a.planDeepPerBlock = a.planDeepStride = 0;
     a.planPacked = nullptr;
     a.packBases = nullptr;
     launchSlabFamily<T, true>(handle, a);
@@ -1719,7 +1710,7 @@ static void ellSpmv(spgpuHandle_t handle, ApiT* z, const ApiT* y, ApiT alpha, co
     a.planBlocks = nullptr;
     a.planDeepSubs = nullptr;
     a.planFlags = nullptr;
-    a.planDeep = a.planMainBlocks = a.planDeepPerBlock = a.planDeepStride = a.planDeepRuns = 0;
+    a.planDeep = a.planMainBlocks = a.planDeepPerBlock = a.planDeepStride = 0;
     a.planPacked = nullptr;
     a.packBases = nullptr;
     launchSlabFamily<T, false>(handle, a);

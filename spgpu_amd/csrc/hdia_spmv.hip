@@ -49,17 +49,20 @@ template <typename T> struct HdiaArgs {
     int rows, cols, hackSize;
     int flatDiags;
     int wideIO;
-    int xcdOrder; /* 0: hardware order; 1: XCD-contiguous eighths; n > 1: runs of n blocks per XCD */
 };
 
+/* 512 lanes per workgroup: 3-4 % faster than 256 on 512^3 with the current kernel.  (The first kernel was fastest at 256 and
+ * slowest at 1 024: profiles/r01b_ab_hdia_block_size.txt.) */
+constexpr int kHdiaThreads = 512;
 
-template <typename T, int RPL, bool NT, int UNROLL, int kHdiaThreads>
+template <typename T, int RPL>
 __global__ __launch_bounds__(kHdiaThreads) void hdiaSpmvKernel(const HdiaArgs<T> a)
 {
-    const unsigned block = a.xcdOrder == 0 ? blockIdx.x
-                         : a.xcdOrder == 1 ? xcdContiguous(blockIdx.x, gridDim.x)
-                                           : xcdRuns(blockIdx.x, gridDim.x, (unsigned)a.xcdOrder);
-    const long long strip = (long long)block * kHdiaThreads + threadIdx.x;
+    /* 4 diagonals per stage: with the strip's x values fetched as one 16-byte load the 8-per-stage form needs 97 VGPRs
+     * (5 wavefronts per SIMD) against 56 (8 wavefronts) and is 15 % slower on 512^3 (profiles/r01d_ab_hdia_wide_x.txt) */
+    constexpr int UNROLL = 4;
+    constexpr bool NT = true; /* coefficients are streamed once */
+    const long long strip = (long long)blockIdx.x * kHdiaThreads + threadIdx.x;
     const long long waveRow0 = (strip - (threadIdx.x & (kWave - 1))) * RPL;
     if (waveRow0 >= a.rows)
         return; /* whole wavefront leaves together */
@@ -100,13 +103,13 @@ __global__ __launch_bounds__(kHdiaThreads) void hdiaSpmvKernel(const HdiaArgs<T>
     auto fetch = [&](int dBase, Pack<T, RPL>* vv, int* oo) {
         /* a full stage everywhere in the wavefront: its UNROLL offsets are consecutive ints, one load instead of
          * UNROLL (element-aligned, like the x strips) */
-        const bool whole = UNROLL == 4 && __ballot(dBase + UNROLL > diags) == 0ull;
+        const bool whole = __ballot(dBase + UNROLL > diags) == 0ull;
         if (whole) {
             const Pack<int, 4> o4 = loadPackElementAligned<int, 4>(offs + dBase);
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 vv[u] = loadPack<NT, T, RPL>(vals + (long long)(dBase + u) * a.hackSize);
-                oo[u] = o4.v[u & 3];
+                oo[u] = o4.v[u];
             }
             return;
         }
@@ -195,28 +198,12 @@ __global__ __launch_bounds__(kHdiaThreads) void hdiaSpmvKernel(const HdiaArgs<T>
     }
 }
 
-template <typename T, int RPL, int UNROLL, int kHdiaThreads>
-static void launchHdiaSized(hipStream_t stream, const HdiaArgs<T>& a, bool nt)
+template <typename T, int RPL>
+static void launchHdia(hipStream_t stream, const HdiaArgs<T>& a)
 {
     const long long strips = ((long long)a.rows + RPL - 1) / RPL;
     const unsigned blocks = (unsigned)((strips + kHdiaThreads - 1) / kHdiaThreads);
-    if (nt)
-        hipLaunchKernelGGL((hdiaSpmvKernel<T, RPL, true, UNROLL, kHdiaThreads>), dim3(blocks), dim3(kHdiaThreads), 0, stream, a);
-    else
-        hipLaunchKernelGGL((hdiaSpmvKernel<T, RPL, false, UNROLL, kHdiaThreads>), dim3(blocks), dim3(kHdiaThreads), 0, stream, a);
-}
-
-template <typename T, int RPL, int UNROLL>
-static void launchHdia(hipStream_t stream, const HdiaArgs<T>& a, bool nt)
-{
-    /* SPGPU_HDIA_BLOCK: workgroup size 256 / 512 (default: +3-4 % over 256 on 512^3 with the current kernel) / 1024 */
-    const int block = spgpuTuning()->hdiaBlock;
-    if (block == 1024)
-        launchHdiaSized<T, RPL, UNROLL, 1024>(stream, a, nt);
-    else if (block == 256)
-        launchHdiaSized<T, RPL, UNROLL, 256>(stream, a, nt);
-    else
-        launchHdiaSized<T, RPL, UNROLL, 512>(stream, a, nt);
+    hipLaunchKernelGGL((hdiaSpmvKernel<T, RPL>), dim3(blocks), dim3(kHdiaThreads), 0, stream, a);
 }
 
 template <typename T, typename ApiT>
@@ -241,30 +228,20 @@ static void hdiaSpmv(spgpuHandle_t handle, ApiT* z, const ApiT* y, ApiT alpha, c
     a.hackSize = hackSize;
     a.flatDiags = flatDiags;
 
-    const SpgpuTuning* tune = spgpuTuning();
-    a.xcdOrder = tune->xcdOrder;
     constexpr int WIDE = 16 / (int)sizeof(T);
-    const bool nt = tune->ntLoads != 0;
-    const bool wideOk = WIDE > 1 && hackSize % WIDE == 0 && ((uintptr_t)dM % 16 == 0) && !tune->hdiaNarrow;
+    const bool wideOk = WIDE > 1 && hackSize % WIDE == 0 && ((uintptr_t)dM % 16 == 0);
 
     hipStream_t stream = handle->currentStream;
     if constexpr (WIDE > 1) {
         if (wideOk) {
             a.wideIO = ((uintptr_t)z % 16 == 0) && ((uintptr_t)y % 16 == 0);
-            /* 4 diagonals per stage by default: with the strip's x values fetched as one 16-byte load the 8-per-stage
-             * form needs 97 VGPRs (5 wavefronts per SIMD) against 56 (8 wavefronts) and is 15 % slower on 512^3
-             * (tools/ab_hdia.py, profiles/r01d_ab_hdia_wide_x.txt); SPGPU_HDIA_VARIANT=2 selects it.  XCD-contiguous
-             * block orders and workgroups of 512/1024 lanes are 2-13 % slower than the hardware order with 256. */
-            if (tune->hdiaVariant == 2)
-                launchHdia<T, WIDE, 8>(stream, a, nt);
-            else
-                launchHdia<T, WIDE, 4>(stream, a, nt);
+            launchHdia<T, WIDE>(stream, a);
             spgpuDebugCheck(handle, "hdiaspmv");
             return;
         }
     }
     a.wideIO = 1;
-    launchHdia<T, 1, 4>(stream, a, nt);
+    launchHdia<T, 1>(stream, a);
     spgpuDebugCheck(handle, "hdiaspmv");
 }
 

@@ -57,7 +57,6 @@ template <typename T> struct SpmmArgs {
     int count;      /* right-hand sides in this pass (<= KP*VEC) */
     int tileRows;   /* tiled kernel: X rows the LDS tile can hold */
     int directFill; /* strip kernel: every 16-byte piece of a tile row is 16 valid, aligned bytes of X (global_load_lds) */
-    int bandMode;   /* strip kernel: wavefronts whose rows form a band take the sliding-window loop (SPGPU_SPMM_VARIANT=11: never) */
     long long ldX, ldYZ;
 };
 
@@ -653,7 +652,7 @@ __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3,
      * never looks at an index again (the head's 32 registers are dead in that loop: the window takes their place).  It is the
      * SpMM counterpart of the SpMV's strip x loads.  Same products, added in the same order: ascending k. */
     int bandBase = -1; /* relative to lo; wavefront-uniform */
-    if (a.bandMode && useTile && groupLongest > 0 && groupLongest <= kStageCols * HEAD && groupLongest % (kStageCols * TRIP) == 0) {
+    if (useTile && groupLongest > 0 && groupLongest <= kStageCols * HEAD && groupLongest % (kStageCols * TRIP) == 0) {
         const int base = __builtin_amdgcn_readfirstlane(head[0].v[0] - a.baseIndex - lo);
         bool off = false;
 #pragma unroll
@@ -922,8 +921,7 @@ template <typename T, int TRIP, int VEC = 2> static void launchSpmmStrips(hipStr
     a.tileRows = kStripTileBytes / (8 * VEC * (int)sizeof(T));
     /* whole tile rows of valid bytes: all KP * VEC right-hand sides present, rows of X 16-byte aligned */
     a.directFill = a.count == 8 * VEC && (8 * VEC * sizeof(T)) % 16 == 0 && (uintptr_t)a.X % 16 == 0 &&
-                   (a.ldX * (long long)sizeof(T)) % 16 == 0 && spgpuTuning()->spmmVariant != 10;
-    a.bandMode = spgpuTuning()->spmmVariant != 11;
+                   (a.ldX * (long long)sizeof(T)) % 16 == 0;
     const size_t lds = kStripTileBytes + (kSpmmThreads / kWave) * sizeof(SpmmStage<T>);
     hipLaunchKernelGGL((hellSpmmStripKernel<T, TRIP, VEC>), dim3(blocks), dim3(kSpmmThreads), lds, stream, a);
 }
@@ -972,35 +970,21 @@ static void hellSpmm(spgpuHandle_t handle, T* Z, const T* Y, T alpha, const T* c
         a.ldYZ = ldYZ;
         a.tileRows = 0;
         a.directFill = 0;
-        a.bandMode = 0;
         const bool pairs = pairsOk && a.count % 2 == 0;
         /* 16-byte loads of whole 32-row half columns */
         const bool strips = pairs && hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0;
-        const int variant = spgpuTuning()->spmmVariant; /* experiments, include/spgpu/tuning.h */
         if (a.count > 8) {
-            if (pairs && variant == 1)
-                launchSpmm<T, 8, 2, 2>(stream, a);          /* plain: X rows through L1 */
-            else if (pairs && variant == 2)
-                launchSpmm<T, 8, 2, 8, true>(stream, a);    /* tiled, 8 slab columns per trip */
-            else if (pairs && variant == 3)
-                launchSpmm<T, 8, 2, 4>(stream, a);
-            else if (variant == 4)
-                launchSpmm<T, 16, 1, 2>(stream, a);
-            else if (pairs && variant == 5)
-                launchSpmm<T, 8, 2, 2, true>(stream, a);    /* tiled, 2 slab columns per trip */
-            else if (pairs && (variant == 6 || !strips))
+            if (strips)
+                launchSpmmStrips<T, 2>(stream, a);          /* X window in LDS when it fits, 16-byte loads */
+            else if (pairs)
                 launchSpmm<T, 8, 2, 4, true>(stream, a);    /* tiled, one row per loader lane */
-            else if (strips)
-                launchSpmmStrips<T, 2>(stream, a);          /* default: X window in LDS when it fits, 16-byte loads */
             else
                 launchSpmm<T, 16, 1, 2>(stream, a);
         } else if (a.count > 4) {
             /* 5 to 8 right-hand sides: the strip kernel with one per lane (64-byte X rows for fp64; no pairing, so odd
              * counts and odd leading dimensions too) */
             const bool strips1 = hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0;
-            if (strips1 && variant == 9 && pairs)
-                launchSpmmStrips<T, 2>(stream, a);          /* experiment: the 16-rhs form with half of each team idle */
-            else if (strips1 && variant != 1)
+            if (strips1)
                 launchSpmmStrips<T, 2, 1>(stream, a);
             else if (pairs)
                 launchSpmm<T, 4, 2, 4>(stream, a);
@@ -1009,7 +993,7 @@ static void hellSpmm(spgpuHandle_t handle, T* Z, const T* Y, T alpha, const T* c
         } else {
             /* 4: the strip kernel with half of each team idle still wins (banded 0.58 vs 0.63 ms, windowed 1.54 vs
              * 1.72 ms); 1-3: the small-team plain kernel is as fast or faster on scattered columns */
-            if (a.count == 4 && variant != 1 && hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0)
+            if (a.count == 4 && hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0)
                 launchSpmmStrips<T, 2, 1>(stream, a);
             else
                 launchSpmm<T, 4, 1, 4>(stream, a);

@@ -32,12 +32,7 @@
 
 namespace spgpu {
 
-constexpr int kL1MaxBlocksDefault = 16384; /* measured: 2 048 -> 64.7 %, 16 384 -> 71 % of 8 TB/s for axpby (tile-stride loop beyond) */
-static int l1MaxBlocks()
-{
-    const int asked = spgpuTuning()->l1Blocks; /* experiments, include/spgpu/tuning.h */
-    return asked >= 1 ? asked : kL1MaxBlocksDefault;
-}
+constexpr int kL1MaxBlocks = 16384; /* measured: 2 048 -> 64.7 %, 16 384 -> 71 % of 8 TB/s for axpby (tile-stride loop beyond) */
 
 /* ---- axpby ---------------------------------------------------------------
  * Expression trees (reference): S/D  alpha*x + beta*y   (daxpby.cu:40-43)
@@ -147,17 +142,16 @@ static void axpbyLaunch(spgpuHandle_t handle, ApiT* zApi, int n, ApiT betaApi, A
                       (!hasBeta || (uintptr_t)y % 16 == 0) && (count == 1 || pitch % WIDE == 0);
     const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
     long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    const long long cap = l1MaxBlocks() / (count < l1MaxBlocks() ? count : l1MaxBlocks());
+    const long long cap = kL1MaxBlocks / (count < kL1MaxBlocks ? count : kL1MaxBlocks);
     if (blocks > (cap > 1 ? cap : 1))
         blocks = cap > 1 ? cap : 1;
     const dim3 grid((unsigned)blocks, (unsigned)count);
     hipStream_t s = handle->currentStream;
     /* Vectors larger than the 256 MiB Infinity Cache cannot be found there again by the next kernel: stream them
      * with the non-temporal hint (measured, n = 1e8: 70-71 % -> 75.5-77 % of the HBM peak, profiles/r01d_level1_nt.txt).
-     * Smaller ones -- the vectors of a solver iteration -- stay cached.  SPGPU_L1_NT = 0 / 1 forces the choice. */
+     * Smaller ones -- the vectors of a solver iteration -- stay cached. */
     const long long streamed = (long long)n * (long long)sizeof(T) * count * (2 + (hasBeta ? 1 : 0));
-    const int ntKnob = spgpuTuning()->l1Nt;
-    const bool nt = (ntKnob < 0 ? streamed >= (256ll << 20) : ntKnob != 0); /* exact aliasing of z is fine: a lane reads its elements before it writes them */
+    const bool nt = streamed >= (256ll << 20); /* exact aliasing of z is fine: a lane reads its elements before it writes them */
 
 #define SPGPU_AXPBY_GO(VEC)                                                                               \
     do {                                                                                                  \
@@ -316,9 +310,8 @@ static void reduceVectors(spgpuHandle_t handle, typename AccOf<T, MODE>::type* o
             blocks = cap;
         const dim3 grid((unsigned)blocks, (unsigned)vectors);
 
-        const int ntKnob = spgpuTuning()->l1Nt;
         const long long streamed = (long long)n * (long long)sizeof(T) * vectors * (MODE == kDot ? 2 : 1);
-        if (wide && (ntKnob < 0 ? streamed >= (256ll << 20) : ntKnob != 0))
+        if (wide && streamed >= (256ll << 20))
             hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE, true>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
                                (long long)pitch);
         else if (wide)
@@ -407,8 +400,8 @@ static void axpbyFromDevice(spgpuHandle_t handle, T* z, int n, int hasBeta, cons
     const bool wide = ((uintptr_t)z % 16 == 0) && ((uintptr_t)x % 16 == 0) && (!hasBeta || !y || (uintptr_t)y % 16 == 0);
     const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
     long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    if (blocks > l1MaxBlocks())
-        blocks = l1MaxBlocks();
+    if (blocks > kL1MaxBlocks)
+        blocks = kL1MaxBlocks;
     hipStream_t s = handle->currentStream;
     if (wide)
         hipLaunchKernelGGL((axpbyDeviceKernel<T, WIDE>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, z, n, hasBeta, betaNum,
@@ -517,15 +510,14 @@ static void mapLaunch(spgpuHandle_t handle, ApiT* outApi, int n, ApiT alphaApi, 
                       (count == 1 || pitch % WIDE == 0);
     const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
     long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    const long long cap = l1MaxBlocks() / (count < l1MaxBlocks() ? count : l1MaxBlocks());
+    const long long cap = kL1MaxBlocks / (count < kL1MaxBlocks ? count : kL1MaxBlocks);
     if (blocks > (cap > 1 ? cap : 1))
         blocks = cap > 1 ? cap : 1;
     const dim3 grid((unsigned)blocks, (unsigned)count);
     hipStream_t s = handle->currentStream;
     /* same rule as axpby: streams beyond the Infinity Cache go non-temporal */
-    const int ntKnob = spgpuTuning()->l1Nt;
     const long long streamed = (long long)n * (long long)sizeof(T) * count * (OP == kAxypbz ? 4 : OP == kAxy ? 3 : 2);
-    if (wide && (ntKnob < 0 ? streamed >= (256ll << 20) : ntKnob != 0))
+    if (wide && streamed >= (256ll << 20))
         hipLaunchKernelGGL((mapKernel<T, WIDE, OP, true>), grid, dim3(kL1Threads), 0, s, out, n, alpha, beta, x, y, z,
                            (long long)pitch, alphaIsOne);
     else if (wide)
@@ -590,7 +582,7 @@ template <typename T> __global__ __launch_bounds__(kL1Threads) void fillKernel(T
 static unsigned sparseGrid(long long count)
 {
     long long blocks = (count + kL1Threads - 1) / kL1Threads;
-    return (unsigned)(blocks > 4 * l1MaxBlocks() ? 4 * l1MaxBlocks() : (blocks < 1 ? 1 : blocks));
+    return (unsigned)(blocks > 4 * kL1MaxBlocks ? 4 * kL1MaxBlocks : (blocks < 1 ? 1 : blocks));
 }
 
 template <typename T, typename ApiT>

@@ -295,7 +295,7 @@ static bool packPlan(SpgpuSpmvPlan* plan, spgpuHandle_t handle, hipStream_t stre
 
 /* ---- host ---------------------------------------------------------------------------------------------------------- */
 
-/* Wave-wide loads per stage of the PACKED kernels beyond the unpacked kernels' (SPGPU_RAGGED_UNROLL).  A stage of the queue kernel
+/* Wave-wide loads per stage of the PACKED kernels beyond the unpacked kernels' (kRaggedUnroll).  A stage of the queue kernel
  * is a memory round trip and a stage with 16-bit indices is a sixth smaller, so the same bytes in flight could be a third more
  * columns per round trip; the order of additions would not depend on it (a phase adds its columns in ascending order whatever
  * the stage size; the chunks of a split sub-group are sized by the unpacked kernels' stage, raggedSplit).  MEASURED with 1
@@ -304,9 +304,7 @@ static bool packPlan(SpgpuSpmvPlan* plan, spgpuHandle_t handle, hipStream_t stre
  * alive instead of 16) leaves the scratch where it is: the ring of three stages is what does not fit.  0 it stays.
  * Workgroups of 6 wavefronts at 3 per SIMD (168 VGPRs: 4 or 5 loads per stage without scratch) instead: 0.66-0.70 -> 1.01-1.05 ms
  * on the frozen target -- fewer, longer-lived wavefronts lose more than the deeper stage wins.  Not kept either. */
-#ifndef SPGPU_PACKED_MORE_UNROLL
-#define SPGPU_PACKED_MORE_UNROLL 0
-#endif
+constexpr int kPackedMoreUnroll = 0;
 
 static size_t roundUp16(size_t v)
 {
@@ -370,8 +368,8 @@ static void startPlan(spgpuHandle_t handle, SpgpuSpmvPlan* plan, hipStream_t str
 /*
  * The ordered SpMV of launchSlabFamily (ellpack_spmv.hip) with the matrix's plan, if it has one that is ready: true = launched,
  * nothing is to follow; false = the caller runs the path with the deep list (and, where that is possible, the analysis has been
- * started behind the scenes).  `shape`: launchRagged's (4: 2 048 rows per workgroup with staged results; 5: 1 024 rows,
- * staged; otherwise 1 024 rows and a 64 KiB tile); tiled = false: the gather form (512 rows, no x tile).
+ * started behind the scenes).  `shape`: launchRagged's (4: 2 048 rows per workgroup with staged results; otherwise 1 024
+ * rows and a 64 KiB tile); tiled = false: the gather form (512 rows, no x tile).
  * mustLaunch: the caller has no deep list for this stream -- without a ready plan the same kernel runs with NO plan: nothing
  * is listed, every sub-group deeper than the cap is worked off by its own block behind its stream, no x tile.  Stateless,
  * slower, the same bits.
@@ -384,10 +382,10 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
 {
     const bool prepareOnly = prepareMode != 0;
     constexpr int RPL = 16 / (int)sizeof(T);
-    constexpr int UNROLL = SPGPU_RAGGED_UNROLL(RPL);
+    constexpr int UNROLL = kRaggedUnroll<RPL>;
     const SpgpuTuning* tune = spgpuTuning();
-    const bool staged = tiled && sizeof(T) <= 8 && (shape == 4 || shape == 5);
-    const int subs = !tiled ? 16 : (staged && shape == 4 ? 64 : 32);
+    const bool staged = tiled && sizeof(T) <= 8 && shape == 4;
+    const int subs = !tiled ? 16 : (staged ? 64 : 32);
     SlabArgs<T> a = in;
     a.split = raggedSplit<T>(a.deepCap, (kWave / (32 / RPL)) * UNROLL, tune->raggedSplit);
     a.deepHeader = nullptr;
@@ -396,24 +394,22 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
     a.planDeep = 0;
     a.planFlags = nullptr;
     a.planPacked = nullptr;
-    int perBlock = tune->planDeepPerBlock;
-    perBlock = perBlock < 1 ? 1 : (perBlock > kPlanDeepMost ? kPlanDeepMost : perBlock);
-    a.planDeepPerBlock = perBlock;
-    a.planDeepRuns = tune->planDeepRuns;
+    a.planDeepPerBlock = kPlanDeepMost;
     a.planDeepStride = 0;
     const long long subGroups = ((long long)a.rows + 31) / 32;
     a.planMainBlocks = (int)((subGroups + subs - 1) / subs);
     auto launch = [&]() {
-        const unsigned deepBlocks = (unsigned)((a.planDeep + perBlock - 1) / perBlock);
+        const unsigned deepBlocks = (unsigned)((a.planDeep + kPlanDeepMost - 1) / kPlanDeepMost);
         const unsigned grid = (unsigned)a.planMainBlocks + deepBlocks;
-        /* the workgroups of deep sub-groups over the first planDeepSpread per cent of the grid (0: all in front; < 0: all behind) */
-        if (tune->planDeepSpread < 0 || deepBlocks == 0u) {
+        /* the workgroups of deep sub-groups spread over the first 60 % of the grid */
+        if (deepBlocks == 0u) {
             a.planDeepStride = 0;
         } else {
-            const unsigned long long reach = (unsigned long long)grid * (unsigned)(tune->planDeepSpread > 100 ? 100 : tune->planDeepSpread) / 100ull;
+            const unsigned long long reach = (unsigned long long)grid * 60ull / 100ull;
             const unsigned stride = (unsigned)(reach / deepBlocks);
             /* odd: the hardware deals workgroup ids round-robin over the 8 XCDs -- with an even stride the long-lived workgroups
-             * would pile up on one or two of them (measured: stride 8, 0.73 -> 0.94 ms, one XCD still busy 250 us after the others) */
+             * would pile up on one or two of them (measured: stride 8, 0.73 -> 0.94 ms, one XCD still busy 250 us after the others).
+             * In the grid: stride <= 1.5 x (reach / deepBlocks) when that is >= 1, so (deepBlocks - 1) x stride < 1.5 x reach <= 0.9 x grid. */
             a.planDeepStride = (int)(stride < 1u ? 1u : (stride | 1u));
         }
 #define SPGPU_PLANNED(WAVES, TILE, SUBS, ZB)                                                                          \
@@ -422,18 +418,14 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
             SPGPU_PLANNED(4, 0, 16, 0);
         } else if constexpr (sizeof(T) <= 8) {
 #define SPGPU_PLANNED_PACKED(WAVES, TILE, SUBS, ZB)                                                                   \
-    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL + SPGPU_PACKED_MORE_UNROLL, WAVES, TILE, SUBS, true, ZB, true, true>), dim3(grid), dim3((WAVES) * kWave), 0, stream, a)
+    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL + kPackedMoreUnroll, WAVES, TILE, SUBS, true, ZB, true, true>), dim3(grid), dim3((WAVES) * kWave), 0, stream, a)
             if (a.planPacked) { /* a frozen matrix: 16-bit indices */
-                if (staged && shape == 4)
+                if (staged)
                     SPGPU_PLANNED_PACKED(8, 49152, 64, 17408);
-                else if (staged)
-                    SPGPU_PLANNED_PACKED(8, 49152, 32, 17408);
                 else
                     SPGPU_PLANNED_PACKED(8, 65536, 32, 0);
-            } else if (staged && shape == 4)
+            } else if (staged)
                 SPGPU_PLANNED(8, 49152, 64, 17408);
-            else if (staged)
-                SPGPU_PLANNED(8, 49152, 32, 17408);
             else
                 SPGPU_PLANNED(8, 65536, 32, 0);
         } else {

@@ -128,20 +128,17 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
     if (spgpuTraceBuffer && threadIdx.x == 0)
         spgpuTraceBuffer[8 * (size_t)blockIdx.x] = wall_clock64();
 #endif
-    /* Consecutive workgroups (in row order) read overlapping slices of x.  The hardware deals workgroup ids round-robin
-     * over the 8 XCDs, each with an L2 of its own: left alone, every slice is fetched from memory by all eight.  With
-     * a.xcdRun > 0 the id is permuted so that runs of xcdRun consecutive row blocks share an XCD (speed only). */
-    unsigned mainId = blockIdx.x, mainBlocks = gridDim.x;
+    unsigned mainId = blockIdx.x; /* the block of rows this workgroup owns */
     if constexpr (PLAN) {
         /* the grid: planMainBlocks workgroups that own blocks of rows, and one for every planDeepPerBlock deep sub-groups.  The
          * latter live long on little bandwidth (their x comes from global memory, a round trip per stage): they are spread
          * over the front part of the grid, one at every planDeepStride-th place, so that they run beside many blocks of rows and
          * are done long before the launch ends (planDeepStride 0: all of them behind the blocks of rows).  Each takes a RUN of
-         * consecutive sub-groups of the list (planDeepRuns; 0: every deepBlocks-th -- "a bit of everything", the first form).  After
-         * an ordering by length the list's neighbours are one window of set-aside long rows: its sub-groups' gathers fall into one
+         * consecutive sub-groups of the list (the first form took every deepBlocks-th -- "a bit of everything").  After an
+         * ordering by length the list's neighbours are one window of set-aside long rows: its sub-groups' gathers fall into one
          * stretch of x and meet in the workgroup's L2, and every window holds about the same work.  Measured on the target, same
          * process and allocations, four rounds each: band 0.7534 -> 0.7465 ms, +-2 048 0.8345 -> 0.8205. */
-        mainBlocks = (unsigned)a.planMainBlocks;
+        const unsigned mainBlocks = (unsigned)a.planMainBlocks;
         const unsigned deepBlocks = gridDim.x - mainBlocks, stride = (unsigned)a.planDeepStride;
         bool deepBlock;
         unsigned deepId;
@@ -156,11 +153,10 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
         }
         if (deepBlock) {
             int count = 0;
-            const bool runs = a.planDeepRuns != 0;
             for (int j = 0; j < a.planDeepPerBlock; ++j)
-                count += (runs ? (long long)deepId * a.planDeepPerBlock + j : (long long)deepId + (long long)j * deepBlocks) < a.planDeep ? 1 : 0;
+                count += (long long)deepId * a.planDeepPerBlock + j < a.planDeep ? 1 : 0;
             wholeSubgroups<T, RPL, IS_HELL, WAVES, TILE_ELEMS * (int)sizeof(T)>(a, tile, count, [&](int j) {
-                return a.planDeepSubs[runs ? deepId * (unsigned)a.planDeepPerBlock + (unsigned)j : deepId + (unsigned)j * deepBlocks];
+                return a.planDeepSubs[deepId * (unsigned)a.planDeepPerBlock + (unsigned)j];
             }, true);
 #ifdef SPGPU_TRACE_BLOCKS
             if (spgpuTraceBuffer && lane == 0)
@@ -169,8 +165,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
             return;
         }
     }
-    const unsigned logicalBlock = a.xcdRun > 0 ? xcdRuns(mainId, mainBlocks, (unsigned)a.xcdRun) : mainId;
-    const long long blockRow0 = (long long)logicalBlock * ROWS;
+    const long long blockRow0 = (long long)mainId * ROWS;
     const T* __restrict__ x = a.x;
 
     /* ---- prologue.  A workgroup lives ~35 us and streams nothing while it finds out where its rows are, so the
@@ -186,7 +181,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
     SpgpuPlanBlock planned{};
     if constexpr (PLAN) {
         if (a.planBlocks) /* (workgroup-uniform: scalar loads, no exchange; no plan: nothing listed, no tile -- the stateless fallback) */
-            planned = a.planBlocks[logicalBlock];
+            planned = a.planBlocks[mainId];
     }
 #pragma unroll
     for (int j = 0; j < RPT; ++j) { /* round trip 1 */
@@ -320,7 +315,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
             }
         }
     };
-    if (!XTILE || !a.stageLate)
+    if (!XTILE)
         stageDestinations();
 
     SPGPU_STAMP(5);
@@ -521,8 +516,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
         for (int q = 0; q < ROUND; ++q)
             if (threadIdx.x + q * BLOCK < pieces)
                 w[q] = loadPackElementAligned<T, PIECE>(from + (size_t)(threadIdx.x + q * BLOCK) * PIECE);
-        if (a.stageLate)
-            stageDestinations(); /* under the tile's and the first stages' round trip */
+        stageDestinations(); /* under the tile's and the first stages' round trip */
 #pragma unroll
         for (int q = 0; q < ROUND; ++q)
             if (threadIdx.x + q * BLOCK < pieces)
@@ -705,7 +699,7 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
             const unsigned long long batch = orphans;
             int count = __popcll(batch);
             count = count < kPlanDeepMost ? count : kPlanDeepMost;
-            const int firstSub = (int)logicalBlock * SUBS;
+            const int firstSub = (int)mainId * SUBS;
             wholeSubgroups<T, RPL, IS_HELL, WAVES, TILE_ELEMS * (int)sizeof(T)>(a, tile, count, [&](int j) {
                 unsigned long long rest = batch;
                 for (int skip = 0; skip < j; ++skip)
@@ -722,10 +716,9 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
 #endif
 }
 
-#ifndef SPGPU_RAGGED_UNROLL
-#define SPGPU_RAGGED_UNROLL(RPL) ((RPL) >= 4 ? 2 : 3) /* wave-wide loads per stage; 3 keeps the 8-byte kernels at 112 VGPRs (4 wavefronts per SIMD: two 8-wavefront workgroups per CU) with two stages in flight */
-#endif
-/* Shapes (SPGPU_RAGGED_SHAPE; 0 is the default, 4 and 5 the staged ones): workgroup lanes / tile / sub-groups per workgroup. */
+/* wave-wide loads per stage; 3 keeps the 8-byte kernels at 112 VGPRs (4 wavefronts per SIMD: two 8-wavefront workgroups per CU) with two stages in flight */
+template <int RPL> constexpr int kRaggedUnroll = RPL >= 4 ? 2 : 3;
+/* Shapes (SPGPU_RAGGED_SHAPE; 0 is the default, 4 the staged one): workgroup lanes / tile / sub-groups per workgroup. */
 /* Returns true if the deep kernels have to follow (false: the launch runs the deep list's items itself). */
 /* Columns per chunk of a split sub-group (raggedSpmvKernel, SPLIT): about 96 (8 stages of the 8-byte kernels), and large
  * enough that the chunk sums of a workgroup whose sub-groups are ALL deepCap deep -- the hacks of set-aside long rows -- fit
@@ -744,7 +737,7 @@ template <typename T> static int raggedSplit(int deepCap, int step, int asked)
 template <typename T, int RPL, bool IS_HELL, bool DEEP>
 static bool launchRagged(hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled)
 {
-    constexpr int UNROLL = SPGPU_RAGGED_UNROLL(RPL);
+    constexpr int UNROLL = kRaggedUnroll<RPL>;
     SlabArgs<T> a = in;
     a.split = raggedSplit<T>(a.deepCap, (kWave / (32 / RPL)) * UNROLL, spgpuTuning()->raggedSplit);
     const long long subs = ((long long)a.rows + 31) / 32;
@@ -758,19 +751,13 @@ static bool launchRagged(hipStream_t stream, const SlabArgs<T>& in, int shape, b
         LAUNCH_RAGGED(4, 0, 16);
         return true;
     }
-    switch (shape) {
-    case 4: /* 2 048 rows per workgroup, results staged by destination */
-    case 5: /* 1 024 rows, staged */
-        if constexpr (sizeof(T) <= 8) { /* (16-byte elements: tile + staging leave room for one workgroup per CU -- the default shape) */
-            if (shape == 4)
-                LAUNCH_RAGGED_Z(8, 49152, 64, 17408);
-            else
-                LAUNCH_RAGGED_Z(8, 49152, 32, 17408);
-            break;
+    if constexpr (sizeof(T) <= 8) { /* (16-byte elements: tile + staging leave room for one workgroup per CU -- the default shape) */
+        if (shape == 4) { /* 2 048 rows per workgroup, results staged by destination */
+            LAUNCH_RAGGED_Z(8, 49152, 64, 17408);
+            return true;
         }
-        [[fallthrough]];
-    default: LAUNCH_RAGGED(8, 65536, 32); break;
     }
+    LAUNCH_RAGGED(8, 65536, 32);
     return true;
 #undef LAUNCH_RAGGED
 #undef LAUNCH_RAGGED_Z

@@ -25,7 +25,8 @@ template <typename T> struct SlabArgs {
     int maxNnz;   /* ELL without rS */
     long long valStride, idxStride; /* elements between two slab columns */
     int wideIO;   /* y and z are aligned for RPL-wide access */
-    int tailLanes; /* TAIL kernels: switch to whole-wave rows when <= this many lanes are busy */
+    int tailLanes; /* TAIL kernels: switch to whole-wave rows when <= this many lanes are busy (always kTailLanes: a runtime
+                    * argument because the constant costs the fp32 and complex fp32 kernels two SGPRs) */
     int* feedback; /* pinned host ints the sample wavefronts report the form they saw to, or NULL */
     int feedbackTag; /* or-ed into every report: the generation of the table entry the report is for (spgpuFormFeedback) */
     long long tileSpanLimit; /* a sample group whose columns span at most this many counts as "local" (x-tile form) */
@@ -39,18 +40,15 @@ template <typename T> struct SlabArgs {
     T* deepPartials;             /* [SPGPU_DEEP_ENTRIES][32] row sums over the columns < deepCap */
     T* deepItemSums;             /* [SPGPU_DEEP_ITEMS][32] */
     int* deepOverflow;           /* pinned: calls that overflowed the list, and what the last of them asked for */
-    int xcdRun;                  /* raggedSpmvKernel: row blocks per XCD run (0: hardware order) */
-    int pipeRanges;              /* pipeSpmvKernel: ranges per workgroup */
     int avgNnzPerRow;            /* the caller's hint (0: none) */
     int split;                   /* raggedSpmvKernel: columns per chunk of a split sub-group (0: none) */
-    int stageLate;               /* raggedSpmvKernel: the destinations are staged under the tile's round trip (SPGPU_STAGE_LATE=0: before the first requests) */
     /* raggedSpmvKernel<..., PLAN> (planned_spmv.hip): the matrix's plan (spgpu_internal.h) */
     const SpgpuPlanBlock* planBlocks; /* [planMainBlocks] */
     const int* planDeepSubs;          /* [planDeep] sub-groups that get workgroups of their own, ascending */
     int planDeep;
     int planMainBlocks;               /* workgroups that own blocks of rows; the rest of the grid owns deep sub-groups */
-    int planDeepPerBlock;             /* deep sub-groups per such workgroup (<= kPlanDeepMost) */
-    int planDeepRuns;                 /* 0: such a workgroup takes sub-groups deepId, deepId + deepBlocks, ... of the list; 1: a run of consecutive ones */
+    int planDeepPerBlock;             /* deep sub-groups per such workgroup: always kPlanDeepMost (as a constant it moves 4 bytes of
+                                       * scratch into the complex fp64 tiled kernel) */
     int planDeepStride;               /* such a workgroup at every planDeepStride-th place of the grid, from the front (0: all of them at the end) */
     int* planFlags;                   /* pinned; [1] = 1: a kernel found the plan contradicting the matrix */
     const int* packBases;             /* slabSpmvKernel<..., PACKED> (a frozen matrix without a row order): the column the 16-bit words of

@@ -232,16 +232,7 @@ static inline int spgpuFeedbackSaid(int word, int tag)
 
 /* Environment knobs (include/spgpu/tuning.h), read once and cached: no getenv in a launch path. */
 typedef struct SpgpuTuning {
-    int ntLoads;     /* 1 */
-    int tailLanes;   /* -1: kernel default */
-    int hdiaVariant; /* 0 */
-    int hdiaBlock;   /* 512 */
-    int hdiaNarrow;  /* 0 */
-    int xcdOrder;    /* 0 */
-    int spmmVariant; /* 0 */
-    int l1Blocks;    /* 0: kernel default */
     int xStrips;     /* -1: by feedback */
-    int xTile;       /* -1: by the handle's hint */
     int autoSweep;   /* 1: AUTO may pick the SWEEP form (SPGPU_AUTO_SWEEP=0: never) */
     int poisonScratch; /* 0; SPGPU_POISON_SCRATCH=1 (testing): device scratch the library allocates and does not have to initialise -- the deep lists'
                         * sums, a plan's tables, the reduction scratch -- is filled with 0xFF bytes (NaN / -1) when it is allocated: a kernel that
@@ -249,16 +240,11 @@ typedef struct SpgpuTuning {
     int deepSplit;   /* -1: when rIdx is given */
     int deepCap;     /* 256 */
     int deepKeep;    /* 64: columns of a sub-group deeper than deepCap that stay in the main kernel (-1 or >= deepCap: deepCap) */
-    int raggedShape; /* 0 */
+    int raggedShape; /* 0: a probe picks the ordered kernel's shape per matrix; 4: always the staged 2 048-row shape */
     int raggedSplit; /* -1: about 96 columns per chunk; 0: sub-groups are never cut; > 0: columns per chunk (rounded up to what LDS can park) */
-    int l1Nt;        /* -1: by size */
     int plan;        /* 1: ordered matrices get a per-matrix plan (planned_spmv.hip); 0: never */
-    int planDeepSpread; /* 60: the deep sub-groups' workgroups are spread over the first 60 % of the grid; 0: all in front; < 0: all behind */
-    int planDeepPerBlock; /* 8: deep sub-groups per such workgroup (1 .. 8) */
     int freezeEscapesPct; /* 1: spgpu?SpmvFreeze keeps a 16-bit copy only if at most this many entries in a hundred are escapes (0xFFFF: the column is
                            * in rP after all) -- a matrix with scattered columns gains nothing from the copy and pays for every escape */
-    int planDeepRuns;     /* 1: such a workgroup takes a run of consecutive sub-groups of the list; 0: every deepBlocks-th */
-    int stageLate;   /* 1: the queue kernel stages its destinations under the tile's round trip (0: before the first requests, as round 3) */
 } SpgpuTuning;
 const SpgpuTuning* spgpuTuning(void);
 

@@ -133,13 +133,13 @@ def test_stale_plan_same_bits_then_rebuilt(gpu, letter):
     assert capi.plan_counts(gpu)[2] == stales + 1   # the new plan fits
 
 
-@pytest.mark.parametrize("keep,split,per_block,spread", [(-1, -1, 4, -1), (0, 48, 1, 0), (64, 0, 8, 100), (32, 150, 3, 37)])
-def test_planned_knobs_keep_the_oracle_order(gpu, tuning, keep, split, per_block, spread):
+@pytest.mark.parametrize("keep,split", [(-1, -1), (0, 48), (64, 0), (32, 150)])
+def test_planned_knobs_keep_the_oracle_order(gpu, tuning, keep, split):
     """SPGPU_DEEP_KEEP / SPGPU_RAGGED_SPLIT change the chunks of a sub-group (and so the bits) for the list path and the planned path
-    alike -- the oracle restates them; SPGPU_PLAN_DEEP_PER_BLOCK / SPGPU_PLAN_DEEP_SPREAD only move work around."""
+    alike -- the oracle restates them."""
     import torch
     from spgpu_amd import capi, formats, synth
-    tuning(SPGPU_DEEP_KEEP=keep, SPGPU_RAGGED_SPLIT=split, SPGPU_PLAN_DEEP_PER_BLOCK=per_block, SPGPU_PLAN_DEEP_SPREAD=spread)
+    tuning(SPGPU_DEEP_KEEP=keep, SPGPU_RAGGED_SPLIT=split)
     n = 5 * 2048 + 9
     h = _matrix(gpu, n, "D", 2048, 100, True, longest=1200, seed=5, near=700)
     x = synth.values_for("D", 51, n)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU box experiment (needs the -DSPGPU_TRACE_BLOCKS build, SPGPU_LIB=...): the queue kernel (raggedSpmvKernel) on the ordered
 power-law matrix: start, tile-in-place and end of every workgroup -> how much of the launch is prologue, stream, ramp and tail.
-  python tools/exp_ragged_trace.py [rows] [window:long] [powerlaw|even] ; EXP_PATTERN=near|band ; SPGPU_RAGGED_SHAPE=0|4|5 ; EXP_ALIGNED=1: spgpuOellOrderAlignedDevice"""
+  python tools/exp_ragged_trace.py [rows] [window:long] [powerlaw|even] ; EXP_PATTERN=near|band ; SPGPU_RAGGED_SHAPE=0|4 ; EXP_ALIGNED=1: spgpuOellOrderAlignedDevice"""
 import ctypes as C
 import os
 import sys
@@ -44,11 +44,11 @@ torch.cuda.synchronize()
 capi.lib.spgpuDebugSetTrace(None)
 everything = trace[:8 * (groups + extra)].view(groups + extra, 8).cpu().numpy().astype(np.float64)
 ran = everything[:, 0] > 0
-spread = int(os.environ.get("SPGPU_PLAN_DEEP_SPREAD", "60"))
+spread = 60       # per cent of the grid the library spreads the deep sub-groups' workgroups over (launchPlanned)
 deep_blocks = int(ran.sum()) - groups
 print(f"plan counts {capi.plan_counts(handle)}; workgroups that ran: {int(ran.sum())} = {groups} blocks of rows + {deep_blocks} of deep sub-groups (spread {spread})")
 grid = groups + deep_blocks
-stride = 0 if spread < 0 or deep_blocks == 0 else max(1, (grid * min(spread, 100) // 100) // deep_blocks) | 1
+stride = 0 if deep_blocks == 0 else max(1, (grid * spread // 100) // deep_blocks) | 1
 ids = np.arange(grid)
 is_deep = (ids >= groups) if stride == 0 else ((ids % stride == 0) & (ids // stride < deep_blocks))
 t = everything[:grid][~is_deep]

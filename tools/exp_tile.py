@@ -6,8 +6,7 @@ length (spgpuOellOrderDevice).  Every timing is followed by an oracle check of t
     python tools/exp_tile.py [D|S] [rows] [cases: uniform,mild,powerlaw]
 
 Environment: EXP_FORMS = comma list of  auto | gather | strips | tile (x tile in LDS) | sweep | raggedN (the kernel for ordered
-rows, workgroup shape N) | raggedg (the same with plain gathers); a suffix xR (ragged0x4) runs it with R consecutive row
-blocks per XCD.  EXP_PATTERNS = near,band,random (power-law) or near2048,near512,window,banded (uniform);
+rows, workgroup shape N: 0 or 4) | raggedg (the same with plain gathers).  EXP_PATTERNS = near,band,random (power-law) or near2048,near512,window,banded (uniform);
 EXP_ORDERS = window:longRows pairs (2048:256,...); EXP_ONLY_WINDOWED=1 skips the plain and globally sorted layouts;
 EXP_WINDOWS_FOR_ALL=1 runs the windowed orders on scattered columns too; EXP_ALIGNED=1 orders the rows with spgpuOellOrderAlignedDevice
 (windows counted among the short rows: one window = one workgroup; DESIGN.md section 3.1);
@@ -93,8 +92,7 @@ def run(h, label, forms):
         os.environ["SPGPU_DEEP_KEEP"] = keep or os.environ.get("EXP_DEEP_KEEP", "64")
         full, _, split = full.partition("@")        # "ragged0@0": sub-groups never cut; "ragged4@48": chunks of 48 columns
         os.environ["SPGPU_RAGGED_SPLIT"] = split or "-1"
-        form, _, xcd = full.partition("x")          # "ragged0x4": shape 0 with runs of 4 row blocks per XCD
-        os.environ["SPGPU_XCD_ORDER"] = xcd or os.environ.get("EXP_XCD_ORDER", "0")
+        form = full
         os.environ["SPGPU_RAGGED_SHAPE"] = form[6:] if form.startswith("ragged") and form[6:].isdigit() else "0"      # raggedN: shape N with the tile; raggedg: gathers
         capi.spgpuTuningReload()
         capi.spgpuSetSpmvForm(handle, 1 if form == "raggedg" else 0 if form.startswith("ragged") else FORMS[form])
@@ -117,7 +115,7 @@ def run(h, label, forms):
         print(f"{letter} {label:46s} {name:10s} slots/nnz {h['slots'] / h['nnz']:.3f}  {t:.4f} ms  {alg / t * 1e-6:7.1f} GB/s  "
               f"{alg / t * 1e-6 / 8000:.3f} of 8 TB/s  {check(h, form)}  plans(uses,builds,stales)={capi.plan_counts(handle)}", flush=True)
     capi.spgpuSetSpmvForm(handle, 0)
-    # EXP_SWEEP="SPGPU_PLAN_DEEP_SPREAD=0,30,60;SPGPU_PLAN_DEEP_PER_BLOCK=2,4": every combination on THIS matrix in THESE allocations
+    # EXP_SWEEP="SPGPU_DEEP_KEEP=32,64;SPGPU_RAGGED_SPLIT=48,96": every combination on THIS matrix in THESE allocations
     # (the time of a kernel moves by several per cent with the placement of the arrays: A/B only inside one process), round-robin,
     # EXP_SWEEP_REPS times
     if os.environ.get("EXP_SWEEP"):

@@ -25,7 +25,7 @@ coo = synth.ragged_coo_on_device(lengths, n, os.environ.get("EXP_PATTERN", "near
 h = formats.coo_to_ordered_hell_device(handle, n, *coo, "D", 32, window, long_rows)
 x = synth.device_vector(n, "D", 3)
 z = torch.zeros(n, dtype=torch.float64, device="cuda")
-rows_per_block = 1024 * (2 if os.environ.get("SPGPU_RAGGED_SHAPE") == "1" else 1)
+rows_per_block = 1024 * (2 if os.environ.get("SPGPU_RAGGED_SHAPE") == "4" else 1)
 blocks = (n + rows_per_block - 1) // rows_per_block
 trace = torch.zeros(3 * blocks + 16, dtype=torch.int64, device="cuda")
 capi.lib.spgpuDebugSetTrace.argtypes = [C.c_void_p]
