@@ -12,7 +12,8 @@
  * gather per nonzero into `count` gathers from `count` cache lines, while the
  * interleaved rows make it ONE 128-byte line for 16 doubles, and they make a
  * rank's row block of X one contiguous buffer for the all-gather.
- * spgpu?mvInterleave / spgpu?mvDeinterleave convert between the two.)
+ * spgpu?mvInterleave / spgpu?mvDeinterleave convert between the two; a caller who holds the pitch layout and whose matrix is
+ * banded or otherwise local can skip the conversion: spgpu?hellspmmMv, spgpu/ext/spmm_mv.h, takes the vectors as they are.)
  *
  * All arrays are device pointers; calls are asynchronous on
  * handle->currentStream.  Z may alias Y exactly.  count <= 0 or rows <= 0 is a

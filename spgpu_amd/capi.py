@@ -142,6 +142,13 @@ for _L in "SD":
     mv_interleave[_L] = _decl(f"spgpu{_L}mvInterleave", None, [Handle, ptr, i32, ptr, i32, i32, i32])
     mv_deinterleave[_L] = _decl(f"spgpu{_L}mvDeinterleave", None, [Handle, ptr, i32, ptr, i32, i32, i32])
 
+# ---- ext/spmm_mv.h: the HELL SpMM on the reference's multivector layout (vector j at base + j*pitch) ----------
+hellspmm_mv = {}
+for _L in "SD":
+    _T = SCALAR[_L]
+    hellspmm_mv[_L] = _decl(f"spgpu{_L}hellspmmMv", None,
+                            [Handle, ptr, ptr, _T, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, ptr, _T, i32, i32, i32, i32])
+
 # ---- ell_conv.h / hell_conv.h / hdia_conv.h (host pointers) --------------------------
 computeEllRowLenghts = _decl("computeEllRowLenghts", None, [ptr, C.POINTER(i32), i32, i32, ptr, i32])
 computeEllAllocPitch = _decl("computeEllAllocPitch", i32, [i32])

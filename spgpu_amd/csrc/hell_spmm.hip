@@ -37,6 +37,7 @@
 #include "spgpu_internal.h"
 
 #include "spgpu/spmm.h"
+#include "spgpu/ext/spmm_mv.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,7 +58,8 @@ template <typename T> struct SpmmArgs {
     int count;      /* right-hand sides in this pass (<= KP*VEC) */
     int tileRows;   /* tiled kernel: X rows the LDS tile can hold */
     int directFill; /* strip kernel: every 16-byte piece of a tile row is 16 valid, aligned bytes of X (global_load_lds) */
-    long long ldX, ldYZ;
+    long long ldX, ldYZ; /* pitch layout (spgpu?hellspmmMv): the pitches of X and of Y / Z */
+    int wideRuns;   /* pitch layout: X, Y, Z 16-byte aligned, pitches multiples of 16 bytes, no rIdx: 16-byte runs along the rows */
 };
 
 constexpr int kSpmmThreads = 256;
@@ -105,7 +107,7 @@ template <typename T> __device__ inline void storeRecord(SpmmRecord<T>* p, T coe
     storePack<uint32_t, 4>(reinterpret_cast<uint32_t*>(p), raw);
 }
 
-template <typename T, int KP, int VEC, int UNROLL, bool FROM_LDS>
+template <typename T, int KP, int VEC, int UNROLL, bool FROM_LDS, bool PITCH = false>
 __device__ inline void spmmAccumulate(const SpmmArgs<T>& a, int lane, int myLen, int groupLongest,
                                       const T* __restrict__ vals, const int* __restrict__ idxs,
                                       const T* __restrict__ tile, int tileFirst, T (&sum)[KP][VEC],
@@ -208,7 +210,8 @@ __device__ inline void spmmAccumulate(const SpmmArgs<T>& a, int lane, int myLen,
             }
         }
     } else {
-        const T* __restrict__ Xsafe = a.X + rhsSafe;
+        /* PITCH (spmm_mv.h): vector j at X + j*ldX, so a lane's VEC right-hand sides of one X row are VEC gathers */
+        const T* __restrict__ Xsafe = a.X + (PITCH ? rhsSafe * a.ldX : (long long)rhsSafe);
         for (int kBase = 0; kBase < groupLongest; kBase += UNROLL) {
             fetch(kBase, coefMine, colMine);
 #pragma unroll
@@ -225,8 +228,15 @@ __device__ inline void spmmAccumulate(const SpmmArgs<T>& a, int lane, int myLen,
                         col[i] = laneFrom(colMine[u], src);
                     }
 #pragma unroll
-                    for (int i = 0; i < CHUNK; ++i) /* no branch: absent entries read row 0 and are discarded below */
-                        xv[i] = loadPack<false, T, VEC>(Xsafe + (long long)(col[i] >= 0 ? col[i] : 0) * a.ldX);
+                    for (int i = 0; i < CHUNK; ++i) { /* no branch: absent entries read row 0 and are discarded below */
+                        if constexpr (PITCH) {
+#pragma unroll
+                            for (int e = 0; e < VEC; ++e) /* a lane whose last vector is past `count` reads its first again */
+                                xv[i].v[e] = Xsafe[(rhsSafe + e < a.count ? e * a.ldX : 0) + (col[i] >= 0 ? col[i] : 0)];
+                        } else {
+                            xv[i] = loadPack<false, T, VEC>(Xsafe + (long long)(col[i] >= 0 ? col[i] : 0) * a.ldX);
+                        }
+                    }
 #pragma unroll
                     for (int i = 0; i < CHUNK; ++i)
 #pragma unroll
@@ -274,12 +284,69 @@ __device__ inline void spmmStore(const SpmmArgs<T>& a, int lane, long long group
     }
 }
 
+/* The epilogue in the pitch layout (spgpu/ext/spmm_mv.h): Z[j*ldYZ + row].  A lane holds KP consecutive rows of its VEC vectors,
+ * i.e. a run of KP elements along the row axis per vector: with a.wideRuns it goes out as 16-byte pieces (the teams of a
+ * wavefront own consecutive runs, so a wavefront covers 64 consecutive rows of each vector), else -- row order, unaligned
+ * arguments, the ragged end, rows an in-place sum skips -- element by element.  Same epilogue arithmetic as spmmStore. */
+template <typename T, int KP, int VEC>
+__device__ inline void spmmStorePitch(const SpmmArgs<T>& a, int lane, long long groupRow0, T (&sum)[KP][VEC])
+{
+    constexpr int RUN = 16 / (int)sizeof(T);
+    static_assert(KP % RUN == 0, "a team's rows are whole 16-byte pieces");
+    const long long row0 = groupRow0 + (lane / KP) * KP;
+    const int rhs0 = (lane % KP) * VEC;
+    const bool hasBeta = isNotZero(a.beta);
+    const bool inPlaceSum = hasBeta && a.Y == a.Z && a.beta == T(1);
+#pragma unroll
+    for (int i0 = 0; i0 < KP; i0 += RUN) {
+        const long long r0 = row0 + i0;
+        bool whole = a.wideRuns && r0 + RUN <= a.rows;
+        if (whole && inPlaceSum) {
+#pragma unroll
+            for (int i = 0; i < RUN; ++i)
+                whole = whole && a.rS[r0 + i] != 0;
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            if (rhs0 + e >= a.count)
+                continue;
+            const long long at0 = (long long)(rhs0 + e) * a.ldYZ;
+            if (whole) {
+                Pack<T, RUN> out;
+                if (hasBeta) {
+                    const Pack<T, RUN> yv = loadPack<false, T, RUN>(a.Y + at0 + r0);
+#pragma unroll
+                    for (int i = 0; i < RUN; ++i)
+                        out.v[i] = epilogue<true>(a.alpha, sum[i0 + i][e], a.beta, yv.v[i]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < RUN; ++i)
+                        out.v[i] = epilogue<false>(a.alpha, sum[i0 + i][e], a.beta, zeroOf<T>());
+                }
+                storePack<T, RUN>(a.Z + at0 + r0, out);
+            } else {
+#pragma unroll
+                for (int i = 0; i < RUN; ++i) {
+                    const long long r = r0 + i;
+                    if (r < a.rows && !(inPlaceSum && a.rS[r] == 0)) {
+                        const long long at = at0 + (a.rIdx ? a.rIdx[r] : r);
+                        a.Z[at] = hasBeta ? epilogue<true>(a.alpha, sum[i0 + i][e], a.beta, a.Y[at])
+                                          : epilogue<false>(a.alpha, sum[i0 + i][e], a.beta, zeroOf<T>());
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0); /* one piece's addresses and y values live at a time */
+    }
+}
+
 /* TILED == false: plain kernel.  TILED == true: the workgroup first finds the window of X rows its 256 matrix rows
  * touch; if the window fits the LDS tile (banded / FEM-like matrices) it is copied into LDS once, coalesced, and the
  * accumulation reads X from there (LDS: 256 B/clk/CU, vector L1: 64); otherwise it accumulates from global memory. */
-template <typename T, int KP, int VEC, int UNROLL, bool TILED>
+template <typename T, int KP, int VEC, int UNROLL, bool TILED, bool PITCH = false>
 __global__ __launch_bounds__(kSpmmThreads) void hellSpmmKernel(const SpmmArgs<T> a)
 {
+    static_assert(!(TILED && PITCH), "the pitch layout's tiled form is the strip kernel");
     extern __shared__ __attribute__((aligned(16))) unsigned char spmmLds[];
     const int lane = threadIdx.x & (kWave - 1);
     const long long group = (long long)blockIdx.x * (kSpmmThreads / kWave) + (threadIdx.x >> 6);
@@ -395,9 +462,12 @@ __global__ __launch_bounds__(kSpmmThreads) void hellSpmmKernel(const SpmmArgs<T>
         if (groupRow0 >= a.rows)
             return;
     } else {
-        spmmAccumulate<T, KP, VEC, UNROLL, false>(a, lane, myLen, groupLongest, vals, idxs, nullptr, 0, sum);
+        spmmAccumulate<T, KP, VEC, UNROLL, false, PITCH>(a, lane, myLen, groupLongest, vals, idxs, nullptr, 0, sum);
     }
-    spmmStore<T, KP, VEC>(a, lane, groupRow0, sum);
+    if constexpr (PITCH)
+        spmmStorePitch<T, KP, VEC>(a, lane, groupRow0, sum);
+    else
+        spmmStore<T, KP, VEC>(a, lane, groupRow0, sum);
 }
 
 
@@ -435,7 +505,11 @@ __device__ inline void waveSync()
 
 /* amdgpu_waves_per_eu(3): the LDS footprint admits 3 wavefronts per SIMD; tell the register allocator to stay
  * within the matching 168 VGPRs instead of trading occupancy for scheduling freedom */
-template <typename T, int TRIP, int VEC>
+/* PITCH: the multivectors of spgpu/ext/spmm_mv.h, vector j at base + j*pitch.  The tile keeps its row-major form, so everything
+ * between the fill and the epilogue -- records, teams, the band window, the order of the additions -- is the code above,
+ * unchanged; the fill transposes `count` runs of X on the way in, a window too wide for the tile costs one gather per
+ * vector, and the epilogue writes runs along the row axis (spmmStorePitch). */
+template <typename T, int TRIP, int VEC, bool PITCH = false>
 __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void hellSpmmStripKernel(const SpmmArgs<T> a)
 {
     constexpr int KP = 8, TILE_LD = KP * VEC; /* VEC right-hand sides per lane: 2 (up to 16 in all) or 1 (up to 8) */
@@ -467,6 +541,55 @@ __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3,
      * lane order from 64 per-lane addresses: lane -> LDS position is fixed, so the lane works out WHICH piece of X lands
      * there (the inverse of tileOffset); only whole wavefronts take it, the ragged end goes through registers. */
     auto fillTile = [&](int first, int count) {
+        if constexpr (PITCH) {
+            /* `first` is a multiple of RUN here (the window's low end is rounded down below), so with a.wideRuns every piece
+             * X[j*ldX + first + RUN*c ..] is 16 aligned bytes.  A lane takes RUN consecutive X rows of ONE vector; the 16 lanes
+             * next to it the same rows of the other vectors (64-byte runs per vector and wavefront in global memory, one
+             * contiguous tile row per 16 lanes in LDS; the rows of a piece are written in an order rotated by the piece's number,
+             * so that the two pieces of a 32-lane LDS pass do not meet in one 256-byte line's banks).  Elements past the
+             * window's high end are not read: the last X row a matrix names may be the last element of its vector. */
+            constexpr int RUN = 16 / (int)sizeof(T);
+            constexpr int FILL = 4;
+            unsigned char* const tileBytes = reinterpret_cast<unsigned char*>(tile);
+            const int j = threadIdx.x % TILE_LD;
+            const bool mine = j < a.count;
+            const T* const xj = a.X + (long long)(mine ? j : 0) * a.ldX + first;
+            if (a.wideRuns) {
+                const int whole = count / RUN;
+                for (int c0 = threadIdx.x / TILE_LD; c0 < whole; c0 += FILL * (kSpmmThreads / TILE_LD)) {
+                    Pack<T, RUN> part[FILL];
+#pragma unroll
+                    for (int f = 0; f < FILL; ++f) {
+                        const int c = c0 + f * (kSpmmThreads / TILE_LD);
+                        if (c < whole && mine)
+                            part[f] = loadPack<false, T, RUN>(xj + c * RUN);
+                    }
+#pragma unroll
+                    for (int f = 0; f < FILL; ++f) {
+                        const int c = c0 + f * (kSpmmThreads / TILE_LD);
+                        if (c < whole && mine) {
+#pragma unroll
+                            for (int e = 0; e < RUN; ++e) {
+                                const int ee = (e + c) % RUN;
+                                T v = part[f].v[0];
+#pragma unroll
+                                for (int q = 1; q < RUN; ++q)
+                                    v = ee == q ? part[f].v[q] : v;
+                                *reinterpret_cast<T*>(tileBytes + tileOffset(c * RUN + ee) + j * (int)sizeof(T)) = v;
+                            }
+                        }
+                    }
+                }
+                for (int r = whole * RUN + threadIdx.x / TILE_LD; r < count; r += kSpmmThreads / TILE_LD)
+                    if (mine)
+                        *reinterpret_cast<T*>(tileBytes + tileOffset(r) + j * (int)sizeof(T)) = xj[r];
+            } else {
+                for (int r = threadIdx.x / TILE_LD; r < count; r += kSpmmThreads / TILE_LD)
+                    if (mine)
+                        *reinterpret_cast<T*>(tileBytes + tileOffset(r) + j * (int)sizeof(T)) = xj[r];
+            }
+            return;
+        }
         constexpr int PIECES_PER_ROW = ROW_BYTES >= 16 ? ROW_BYTES / 16 : 1;
         constexpr int PIECE_ELEMS = 16 / (int)sizeof(T);
         if (ROW_BYTES >= 16 && a.directFill) {
@@ -642,6 +765,8 @@ __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3,
         blockWindow(lo, hi);
     }
     const bool useTile = fitsSoFar && hi >= lo && (long long)hi - lo < a.tileRows; /* workgroup-uniform */
+    if constexpr (PITCH) /* 16-byte pieces of the vectors start at multiples of 16 bytes; a.tileRows leaves room for it */
+        lo = hi >= lo ? lo & ~(16 / (int)sizeof(T) - 1) : lo;
 
     /* BAND wavefronts.  In a band or stencil matrix in natural order row r + 1 names the columns of row r shifted by one, and a
      * row's entries ascend by one: over the 8 rows of a team and 8 slab columns only 15 different X rows occur, each used up to 8
@@ -816,7 +941,7 @@ __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3,
             slab = (long long)a.hackOffsets[hack] + ((unsigned)myRow - hack * hs);
             myLen = a.rS[myRow];
         }
-        spmmAccumulate<T, KP, VEC, 2, false>(a, lane, myLen, groupLongest, a.cM + slab, a.rP + slab, nullptr, 0, sum);
+        spmmAccumulate<T, KP, VEC, 2, false, PITCH>(a, lane, myLen, groupLongest, a.cM + slab, a.rP + slab, nullptr, 0, sum);
     } else {
         const int team = lane / KP;
         const int rhs0 = (lane % KP) * VEC;
@@ -910,7 +1035,10 @@ __global__ __launch_bounds__(kSpmmThreads) __attribute__((amdgpu_waves_per_eu(3,
     }
     if (groupRow0 >= a.rows)
         return;
-    spmmStore<T, KP, VEC>(a, lane, groupRow0, sum);
+    if constexpr (PITCH)
+        spmmStorePitch<T, KP, VEC>(a, lane, groupRow0, sum);
+    else
+        spmmStore<T, KP, VEC>(a, lane, groupRow0, sum);
 }
 
 template <typename T, int TRIP, int VEC = 2> static void launchSpmmStrips(hipStream_t stream, const SpmmArgs<T>& in)
@@ -970,6 +1098,7 @@ static void hellSpmm(spgpuHandle_t handle, T* Z, const T* Y, T alpha, const T* c
         a.ldYZ = ldYZ;
         a.tileRows = 0;
         a.directFill = 0;
+        a.wideRuns = 0;
         const bool pairs = pairsOk && a.count % 2 == 0;
         /* 16-byte loads of whole 32-row half columns */
         const bool strips = pairs && hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0;
@@ -1000,6 +1129,60 @@ static void hellSpmm(spgpuHandle_t handle, T* Z, const T* Y, T alpha, const T* c
         }
     }
     spgpuDebugCheck(handle, "hellspmm");
+}
+
+/* spgpu?hellspmmMv (spgpu/ext/spmm_mv.h): two shapes.  The strip kernel with PITCH for hackSize % 32 == 0 and 16-byte aligned
+ * cM / rP (what the 16-byte matrix loads need) -- two vectors per lane for 9..16 of a pass, one for up to 8; a.wideRuns
+ * switches its fill and epilogue between 16-byte pieces and single elements -- and the one-row-per-lane kernel for
+ * everything else.  More than 16 vectors: passes of 16. */
+template <typename T>
+static void hellSpmmMv(spgpuHandle_t handle, T* Z, const T* Y, T alpha, const T* cM, const int* rP, int hackSize,
+                       const int* hackOffsets, const int* rS, const int* rIdx, int rows, const T* X, T beta,
+                       int baseIndex, int count, int pitchX, int pitchYZ)
+{
+    if (rows <= 0 || count <= 0 || hackSize <= 0)
+        return;
+    hipStream_t stream = handle->currentStream;
+    const long long groups = ((long long)rows + kWave - 1) / kWave;
+    const unsigned blocks = (unsigned)((groups + kSpmmThreads / kWave - 1) / (kSpmmThreads / kWave));
+    const bool strips = hackSize % 32 == 0 && (uintptr_t)cM % 16 == 0 && (uintptr_t)rP % 16 == 0;
+    for (int first = 0; first < count; first += 16) {
+        SpmmArgs<T> a;
+        a.Z = Z + (long long)first * pitchYZ;
+        a.Y = Y ? Y + (long long)first * pitchYZ : nullptr;
+        a.X = X + (long long)first * pitchX;
+        a.cM = cM;
+        a.rP = rP;
+        a.rS = rS;
+        a.rIdx = rIdx;
+        a.hackOffsets = hackOffsets;
+        a.alpha = alpha;
+        a.beta = beta;
+        a.rows = rows;
+        a.baseIndex = baseIndex;
+        a.hackSize = hackSize;
+        a.count = count - first < 16 ? count - first : 16;
+        a.ldX = pitchX;
+        a.ldYZ = pitchYZ;
+        a.tileRows = 0;
+        a.directFill = 0;
+        a.wideRuns = !rIdx && (uintptr_t)a.X % 16 == 0 && (uintptr_t)a.Z % 16 == 0 && (!a.Y || (uintptr_t)a.Y % 16 == 0) &&
+                     ((long long)pitchX * sizeof(T)) % 16 == 0 && ((long long)pitchYZ * sizeof(T)) % 16 == 0;
+        if (strips) {
+            const size_t lds = kStripTileBytes + (kSpmmThreads / kWave) * sizeof(SpmmStage<T>);
+            const int round = 16 / (int)sizeof(T) - 1; /* rows the window grows by when its low end is rounded down */
+            if (a.count > 8) {
+                a.tileRows = kStripTileBytes / (16 * (int)sizeof(T)) - round;
+                hipLaunchKernelGGL((hellSpmmStripKernel<T, 2, 2, true>), dim3(blocks), dim3(kSpmmThreads), lds, stream, a);
+            } else {
+                a.tileRows = kStripTileBytes / (8 * (int)sizeof(T)) - round;
+                hipLaunchKernelGGL((hellSpmmStripKernel<T, 2, 1, true>), dim3(blocks), dim3(kSpmmThreads), lds, stream, a);
+            }
+        } else {
+            hipLaunchKernelGGL((hellSpmmKernel<T, 16, 1, 2, false, true>), dim3(blocks), dim3(kSpmmThreads), 0, stream, a);
+        }
+    }
+    spgpuDebugCheck(handle, "hellspmmMv");
 }
 
 /* Layout conversion through a 32x33 LDS tile so that both sides are coalesced. */
@@ -1064,6 +1247,22 @@ void spgpuDhellspmm(spgpuHandle_t handle, double* Z, const double* Y, double alp
 {
     (void)avgNnzPerRow;
     hellSpmm<double>(handle, Z, Y, alpha, cM, rP, hackSize, hackOffsets, rS, rIdx, rows, X, beta, baseIndex, count, ldX, ldYZ);
+}
+
+void spgpuShellspmmMv(spgpuHandle_t handle, float* Z, const float* Y, float alpha, const float* cM, const int* rP,
+                      int hackSize, const int* hackOffsets, const int* rS, const int* rIdx, int avgNnzPerRow, int rows,
+                      const float* X, float beta, int baseIndex, int count, int pitchX, int pitchYZ)
+{
+    (void)avgNnzPerRow;
+    hellSpmmMv<float>(handle, Z, Y, alpha, cM, rP, hackSize, hackOffsets, rS, rIdx, rows, X, beta, baseIndex, count, pitchX, pitchYZ);
+}
+
+void spgpuDhellspmmMv(spgpuHandle_t handle, double* Z, const double* Y, double alpha, const double* cM, const int* rP,
+                      int hackSize, const int* hackOffsets, const int* rS, const int* rIdx, int avgNnzPerRow, int rows,
+                      const double* X, double beta, int baseIndex, int count, int pitchX, int pitchYZ)
+{
+    (void)avgNnzPerRow;
+    hellSpmmMv<double>(handle, Z, Y, alpha, cM, rP, hackSize, hackOffsets, rS, rIdx, rows, X, beta, baseIndex, count, pitchX, pitchYZ);
 }
 
 void spgpuSmvInterleave(spgpuHandle_t h, float* dst, int ld, const float* src, int pitch, int n, int count)
