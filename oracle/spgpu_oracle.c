@@ -625,7 +625,7 @@ ORC_DEFINE_TYPE(d, double, double)
 ORC_DEFINE_TYPE(c, orc_cfloat, float)
 ORC_DEFINE_TYPE(z, orc_cdouble, double)
 
-/* The MI355X slab kernel's "tail" order (spgpu_amd/csrc/ellpack_spmv.hip, TAIL): a wavefront owns
+/* The MI355X slab kernel's "tail" order (spgpu_amd/csrc/slab_spmv.hip.h, TAIL): a wavefront owns
  * groupRows consecutive rows, rowsPerLane per lane.  It walks slab columns `step` at a time while more than
  * tailLanes lanes still have entries (a strip of rowsPerLane rows keeps `phases` lanes busy); the first
  * column block at which <= tailLanes lanes are busy is tailFrom.  A row's sum is then: `phases` partial sums

@@ -5,7 +5,7 @@
  * After an ordering by length (ellToOell, reference ell.c:85-202; spgpuOellOrder*Device) the long rows sit together: whole
  * hacks are hundreds or thousands of columns deep, far more than a wavefront of the queue kernel should own.  Without a
  * plan such a sub-group registers in the stream's deep list and two launches behind the main kernel finish it
- * (deepItemsKernel / deepFinishKernel, ellpack_spmv.hip).  With a plan the sub-groups are known before the launch, a few
+ * (deepItemsKernel / deepFinishKernel, deep_items.hip.h).  With a plan the sub-groups are known before the launch, a few
  * of them make up a workgroup of the same grid, and that workgroup does everything: its wavefronts take the sub-groups'
  * chunks round-robin, a chunk's sum waits in LDS, a half-wave per sub-group adds the chunk sums in chunk order, applies
  * the epilogue and stores z through rIdx.  No list, no scratch in global memory, no launch behind.

@@ -373,14 +373,14 @@ static void startPlan(spgpuHandle_t handle, SpgpuSpmvPlan* plan, hipStream_t str
  * mustLaunch: the caller has no deep list for this stream -- without a ready plan the same kernel runs with NO plan: nothing
  * is listed, every sub-group deeper than the cap is worked off by its own block behind its stream, no x tile.  Stateless,
  * slower, the same bits.
- * prepareMode 1 (spgpu?SpmvPrepare): nothing is launched but the analysis, and that is waited for: true = the plan is ready.
- * prepareMode 2 (spgpu?SpmvFreeze): the same, and the plan gets its 16-bit copy of the column indices (packPlan): true = the
+ * call Prepare (spgpu?SpmvPrepare): nothing is launched but the analysis, and that is waited for: true = the plan is ready.
+ * call Freeze (spgpu?SpmvFreeze): the same, and the plan gets its 16-bit copy of the column indices (packPlan): true = the
  * matrix is frozen -- later launches read 2 bytes of index per stored entry instead of 4 (raggedSpmvKernel<..., PACKED>).
  */
 template <typename T, bool IS_HELL>
-bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, int prepareMode)
+bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, SpmvCall call)
 {
-    const bool prepareOnly = prepareMode != 0;
+    const bool prepareOnly = call != SpmvCall::Run;
     constexpr int RPL = 16 / (int)sizeof(T);
     constexpr int UNROLL = kRaggedUnroll<RPL>;
     const SpgpuTuning* tune = spgpuTuning();
@@ -437,36 +437,17 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
 
     /* a captured launch carries the plan's addresses for as long as the graph lives, and plans are retired: in a capture only a
      * HELD plan (spgpuSpmvHold, include/spgpu/ext/graph.h), which the host never retires, is used -- looked up, never made */
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
-        (void)hipGetLastError();
-        capturing = hipStreamCaptureStatusActive;
-    }
-    const bool heldOnly = capturing != hipStreamCaptureStatusNone;
+    const bool heldOnly = spgpuStreamCapturing(stream);
     bool launched = false;
     if (tune->plan && in.rIdx && (!heldOnly || !prepareOnly)) {
-        SpgpuSpmvPlan key{};
-        key.rP = in.rP;
-        key.rS = in.rS;
-        key.rIdx = in.rIdx;
-        key.hackOffsets = in.hackOffsets;
-        key.idxStride = in.idxStride;
-        key.rows = in.rows;
-        key.hackSize = in.hackSize;
-        key.baseIndex = in.baseIndex;
-        key.maxNnz = in.maxNnz;
-        key.deepCap = in.deepCap;
-        key.subs = subs;
+        const SpgpuSpmvPlan key = planKey(in, in.rIdx, in.deepCap, subs);
         SpgpuPrivateHandle* h = spgpuPrivate(handle);
-        spgpuPlanLock(handle);
+        spgpuTablesLock(handle);
         SpgpuSpmvPlan* plan = heldOnly ? spgpuPlanFind(handle, &key) : spgpuPlanRecord(handle, &key);
         if (plan && heldOnly && plan->holds <= 0)
             plan = nullptr;
         if (plan) {
-            if (plan->state == SPGPU_PLAN_BUILDING && spgpuEventDone(plan->built)) {
-                plan->deep = ((volatile int*)plan->pinned)[0];
-                plan->state = SPGPU_PLAN_READY;
-            }
+            (void)spgpuPlanLanded(plan, 0);
             if (plan->state == SPGPU_PLAN_READY && plan->holds <= 0 && ((volatile int*)plan->pinned)[1] != 0) {
                 /* a kernel met a sub-group whose depth contradicts the plan: another matrix lives at these addresses now.  (Its
                  * results were right all the same.)  A matrix that keeps changing under a young plan is left alone after the third time.
@@ -481,12 +462,8 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
             if (plan->state == SPGPU_PLAN_EMPTY)
                 startPlan<IS_HELL>(handle, plan, stream);
             if (prepareOnly) {
-                if (plan->state == SPGPU_PLAN_BUILDING && hipEventSynchronize(plan->built) == hipSuccess) {
-                    plan->deep = ((volatile int*)plan->pinned)[0];
-                    plan->state = SPGPU_PLAN_READY;
-                }
-                launched = plan->state == SPGPU_PLAN_READY;
-                if (prepareMode == 2) { /* freeze: true = the plan has its 16-bit indices */
+                launched = spgpuPlanLanded(plan, 1) != 0;
+                if (call == SpmvCall::Freeze) { /* freeze: true = the plan has its 16-bit indices */
                     if (launched && !plan->packed && tiled && sizeof(T) <= 8 && (subs == 64 || subs == 32))
                         (void)packPlan<IS_HELL>(plan, handle, stream);
                     launched = launched && plan->packed != nullptr;
@@ -508,7 +485,7 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
                 launched = true;
             }
         }
-        spgpuPlanUnlock(handle);
+        spgpuTablesUnlock(handle);
     }
     if (!launched && mustLaunch && !prepareOnly) {
         launch();
@@ -517,14 +494,14 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
     return launched;
 }
 
-template bool launchPlanned<float, true>(spgpuHandle_t, hipStream_t, const SlabArgs<float>&, int, bool, bool, int);
-template bool launchPlanned<float, false>(spgpuHandle_t, hipStream_t, const SlabArgs<float>&, int, bool, bool, int);
-template bool launchPlanned<double, true>(spgpuHandle_t, hipStream_t, const SlabArgs<double>&, int, bool, bool, int);
-template bool launchPlanned<double, false>(spgpuHandle_t, hipStream_t, const SlabArgs<double>&, int, bool, bool, int);
-template bool launchPlanned<cfloat, true>(spgpuHandle_t, hipStream_t, const SlabArgs<cfloat>&, int, bool, bool, int);
-template bool launchPlanned<cfloat, false>(spgpuHandle_t, hipStream_t, const SlabArgs<cfloat>&, int, bool, bool, int);
-template bool launchPlanned<cdouble, true>(spgpuHandle_t, hipStream_t, const SlabArgs<cdouble>&, int, bool, bool, int);
-template bool launchPlanned<cdouble, false>(spgpuHandle_t, hipStream_t, const SlabArgs<cdouble>&, int, bool, bool, int);
+template bool launchPlanned<float, true>(spgpuHandle_t, hipStream_t, const SlabArgs<float>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<float, false>(spgpuHandle_t, hipStream_t, const SlabArgs<float>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<double, true>(spgpuHandle_t, hipStream_t, const SlabArgs<double>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<double, false>(spgpuHandle_t, hipStream_t, const SlabArgs<double>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<cfloat, true>(spgpuHandle_t, hipStream_t, const SlabArgs<cfloat>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<cfloat, false>(spgpuHandle_t, hipStream_t, const SlabArgs<cfloat>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<cdouble, true>(spgpuHandle_t, hipStream_t, const SlabArgs<cdouble>&, int, bool, bool, SpmvCall);
+template bool launchPlanned<cdouble, false>(spgpuHandle_t, hipStream_t, const SlabArgs<cdouble>&, int, bool, bool, SpmvCall);
 
 } // namespace spgpu
 

@@ -19,7 +19,7 @@
  *   - the slice of x the workgroup's rows touch is staged in LDS (as in the x-tile form of slabSpmvKernel); entries
  *     outside it are gathered from global memory.
  *   - sub-groups deeper than deepCap keep their first deepCap columns here and hand the rest to the deep kernels
- *     through the handle's deep list (deepRegister; deepItemsKernel and deepFinishKernel in ellpack_spmv.hip).
+ *     through the handle's deep list (deepRegister; deepItemsKernel and deepFinishKernel in deep_items.hip.h).
  *
  * Algorithmic bytes as for slabSpmvKernel, plus 4 per row for rIdx.
  */

@@ -1,7 +1,7 @@
 #pragma once
 /*
  * What the ELL / HELL SpMV kernels are handed (one struct for every kernel of the family), and the pieces more than one
- * translation unit of the family needs: ellpack_spmv.hip (the kernels for rows as they come, the queue kernel for ordered
+ * translation unit of the family needs: ellpack_spmv.hip (the dispatch; the kernels for rows as they come, the queue kernel for ordered
  * rows with its deep list) and planned_spmv.hip (the queue kernel driven by a per-matrix plan).
  */
 #include "numeric.hip.h"
@@ -90,9 +90,31 @@ struct ColumnProbe {
     long long middles; /* sum over sampled rows of (first + last column) / 2 */
 };
 
+/* The key of a matrix' record in the handle's plan table (spgpu_internal.h): the index arrays of `a` and what the record assumes.
+ * rIdx, deepCap and subs as the analysis uses them; a frozen record of a matrix without a row order: NULL, 0 and -rows per group. */
+template <typename T> inline SpgpuSpmvPlan planKey(const SlabArgs<T>& a, const int* rIdx, int deepCap, int subs)
+{
+    SpgpuSpmvPlan key{};
+    key.rP = a.rP;
+    key.rS = a.rS;
+    key.rIdx = rIdx;
+    key.hackOffsets = a.hackOffsets;
+    key.idxStride = a.idxStride;
+    key.rows = a.rows;
+    key.hackSize = a.hackSize;
+    key.baseIndex = a.baseIndex;
+    key.maxNnz = a.maxNnz;
+    key.deepCap = deepCap;
+    key.subs = subs;
+    return key;
+}
+
+/* What the dispatch was entered for.  Run: the SpMV.  Prepare (spgpu?SpmvPrepare): nothing is multiplied -- the choices a first SpMV
+ * would leave to later calls are made now and waited for.  Freeze (spgpu?SpmvFreeze): the same, plus the 16-bit copy of the indices. */
+enum class SpmvCall { Run, Prepare, Freeze };
 
 /* planned_spmv.hip: the ordered SpMV with the matrix's plan, if it has one that is ready (true: launched, nothing follows) */
-template <typename T, bool IS_HELL> bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, int prepareMode);
+template <typename T, bool IS_HELL> bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, SpmvCall call);
 
 constexpr int kDeepChunk = 64; /* columns per deep item; measured: items of 32 / 64 / 128 columns and stages of 16 / 32 within 8 % -- the kernel is bound by the lines its gathers pull */
 

@@ -36,7 +36,8 @@ typedef struct SpgpuPrivateHandle {
     int formCalls[8];                               /* SpMV calls seen for the entry */
     int formGeneration[8];                          /* bumped when the entry is given to another matrix (tags the reports) */
     unsigned formNext;
-    pthread_mutex_t formLock; /* guards formKey / formRows / formNext */
+    pthread_mutex_t tablesLock; /* guards every table of the handle: the form feedback entries, the deep lists' owners, the plans and their
+                                 * graveyard, the adopted matrices, the holds and the counters beside them (spgpuTablesLock) */
     int spmvForm;             /* SPGPU_SPMV_FORM_* set by spgpuSetSpmvForm (atomic) */
     /* deep lists of the ELL/HELL SpMV, one per stream the handle has been given (spgpuCreate: the default stream;
      * spgpuSetStream: every new one): two SpMVs of one handle in flight on two streams never share a list */
@@ -51,7 +52,7 @@ typedef struct SpgpuPrivateHandle {
     int deepFallbacks;                        /* ordered SpMV calls on a stream without a list (spgpuDeepListFallbacks) */
     int deepRecycled;                         /* lists that changed hands (spgpuDeepListsRecycled) */
     int lastSpmvForm;         /* form of the most recent ELL/HELL SpMV launch (diagnostic, atomic) */
-    /* per-matrix plans of the ELL/HELL SpMV with a row order (below; guarded by formLock) */
+    /* per-matrix plans of the ELL/HELL SpMV with a row order (below; guarded by tablesLock) */
     struct SpgpuSpmvPlan* plans;                    /* [SPGPU_PLANS] */
     int* planPinned;                                /* pinned, SPGPU_PLANS * SPGPU_PLAN_WORDS ints */
     void* planGraveyard[SPGPU_PLAN_GRAVES];         /* device buffers of retired plans: kernels in flight may still read them */
@@ -60,7 +61,7 @@ typedef struct SpgpuPrivateHandle {
     int planUses, planBuilds, planStales;           /* diagnostics (spgpuSpmvPlanCounts) */
     int planFreezes;                                /* spgpu?SpmvFreeze calls that left a matrix frozen */
     /* ADOPTED matrices (spgpuHellSpmvAdopt, include/spgpu/tuning.h; csrc/adopted_hell.hip): a HELL matrix without a row order whose rows
-     * are ragged, of which the library keeps its own copy with the rows ordered by length; guarded by formLock */
+     * are ragged, of which the library keeps its own copy with the rows ordered by length; guarded by tablesLock */
     struct SpgpuAdopted* adopted;                   /* [SPGPU_ADOPTED] */
     int adoptedCount;                               /* entries in use: an SpMV without rIdx looks one up only when > 0 */
     int adoptedUses;
@@ -74,14 +75,14 @@ static inline SpgpuPrivateHandle* spgpuPrivate(spgpuHandle_t h)
     return (SpgpuPrivateHandle*)(void*)h;
 }
 
-/* Deep list of the ELL/HELL SpMV (csrc/ellpack_spmv.hip, DEEP form): device memory owned by the handle, allocated on
+/* Deep list of the ELL/HELL SpMV (csrc/ellpack_spmv.hip launchOrdered, csrc/deep_items.hip.h): device memory owned by the handle, allocated on
  * the first call that needs it.  The main kernel registers every 32-row sub-group deeper than deepCap as one ENTRY and
  * its columns beyond the cap as ITEMS of deepChunk columns; deepItemsKernel gives every item to a wavefront,
  * deepFinishKernel adds an entry's item sums in item order, writes z and -- the workgroup that finishes last -- zeroes the
  * header for the next call.  A list belongs to ONE stream of the handle (calls on one stream run in order); the handle
  * keeps a list for each of the first SPGPU_DEEP_STREAMS streams it is given -- allocated in spgpuCreate / spgpuSetStream,
- * never inside an SpMV call -- and an SpMV on a stream without a list runs the kernel that needs none
- * (share_spmv.hip.h). */
+ * never inside an SpMV call -- and an SpMV on a stream without a list runs the queue kernel without a list: from the matrix'
+ * plan if it is ready, else with every deep sub-group worked off by a block of its own (planned_spmv.hip, launchPlanned: mustLaunch). */
 typedef struct SpgpuDeepEntry {
     int row0;      /* first row of the 32-row sub-group (a multiple of 32) */
     int depth;     /* its longest row */
@@ -143,7 +144,7 @@ typedef struct SpgpuSpmvPlan {
     const void *rP, *rS, *rIdx, *hackOffsets;
     long long idxStride;
     int rows, hackSize, baseIndex, maxNnz, deepCap, subs; /* subs: 32-row sub-groups per block; < 0: the frozen record of a matrix WITHOUT a
-                                                           * row order (ellpack_spmv.hip freezeSlab): -rows per group, `device` = the groups' bases */
+                                                           * row order (frozen_slab.hip.h freezeSlab): -rows per group, `device` = the groups' bases */
     /* state */
     int state;      /* SPGPU_PLAN_EMPTY ... */
     int stales;     /* times it was found stale */
@@ -162,14 +163,21 @@ typedef struct SpgpuSpmvPlan {
 enum { SPGPU_PLAN_EMPTY = 0, SPGPU_PLAN_BUILDING = 1, SPGPU_PLAN_READY = 2, SPGPU_PLAN_GIVEN_UP = 3 };
 /* The plan table is used with the handle's lock held from the look-up to the launch that reads the plan's arrays (a second
  * host thread on the handle may retire a plan and free retired buffers only under the same lock, after a device-wide wait). */
-void spgpuPlanLock(spgpuHandle_t h);
-void spgpuPlanUnlock(spgpuHandle_t h);
+void spgpuTablesLock(spgpuHandle_t h);
+void spgpuTablesUnlock(spgpuHandle_t h);
 /* Lock held.  The record with this key; or, if there is none, the least recently used record that is not held, retired and
  * re-keyed (state EMPTY).  NULL: the handle has no plan table (its allocation failed), or every record is held or still being
  * analysed -- the call runs without a plan. */
 SpgpuSpmvPlan* spgpuPlanRecord(spgpuHandle_t h, const SpgpuSpmvPlan* key);
 /* Lock held.  The record with this key, or NULL (nothing is retired, nothing re-keyed). */
 SpgpuSpmvPlan* spgpuPlanFind(spgpuHandle_t h, const SpgpuSpmvPlan* key);
+/* Lock held.  A record whose analysis has completed becomes READY (wait != 0: the analysis is waited for).  1 = the record is READY. */
+int spgpuPlanLanded(SpgpuSpmvPlan* plan, int wait);
+/* Lock held.  Counts the frozen records of matrices without a row order again (planFrozenSlabs): after a Freeze and after a Thaw. */
+void spgpuPlanCountFrozenSlabs(spgpuHandle_t h);
+/* spgpuCreate / spgpuDestroy: the per-matrix tables (spmv_records.c). */
+void spgpuRecordsCreate(SpgpuPrivateHandle* h);
+void spgpuRecordsDestroy(SpgpuPrivateHandle* h);
 /* An adopted matrix: the caller's arrays (the key) and the library's ordered copy of them. */
 #define SPGPU_ADOPTED 4
 typedef struct SpgpuAdopted {
@@ -210,6 +218,18 @@ static inline int spgpuEventDone(hipEvent_t event)
     if (said != hipSuccess && hipPeekAtLastError() == said) /* "not ready" (or: recorded inside a capture) is this poll's business only */
         (void)hipGetLastError();
     return said == hipSuccess;
+}
+
+/* Is `stream` being captured into a graph?  A query that fails counts as "yes" (the caller then touches nothing a graph could
+ * outlive), and its error is taken back. */
+static inline int spgpuStreamCapturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &status) != hipSuccess) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    return status != hipStreamCaptureStatusNone;
 }
 
 /* With -DSPGPU_DEBUG every launch is followed by a synchronising error check

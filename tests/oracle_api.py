@@ -475,7 +475,7 @@ def slab_shape(letter, form="gather", deep_cap=0, split=-1, deep_keep=None):
         deep_keep = int(os.environ.get("SPGPU_DEEP_KEEP", DEEP_KEEP))
     deep_keep = deep_keep if 0 <= deep_keep < deep_cap else deep_cap
     deep = dict(deep_cap=deep_cap, deep_keep=deep_keep, **DEEP_SHAPE[letter]) if deep_cap > 0 else {}
-    if form == "share":    # shareSpmvKernel (csrc/share_spmv.hip.h): (sub-group, chunk) items, 48 columns per chunk, the
+    if form == "share":    # the retired shareSpmvKernel's order: (sub-group, chunk) items, 48 columns per chunk, the
         phases = 2 * rpl   # chunk sums of a sub-group added in chunk order
         return dict(group_rows=32, rows_per_lane=rpl, step=phases * (2 if rpl >= 4 else 3), tail_lanes=0, phases=phases,
                     deep_cap=SHARE_CHUNK, deep_phases=phases, deep_chunk=SHARE_CHUNK)

@@ -220,7 +220,7 @@ def test_frozen_ell(gpu, tuning):
     assert capi.spgpuSpmvThaw(gpu, _dp(dev.rP)) == capi.SPGPU_SUCCESS
 
 
-# ---- matrices WITHOUT a row order: the default kernels' frozen form (ellpack_spmv.hip freezeSlab, slabSpmvKernel<..., PACKED>) ----
+# ---- matrices WITHOUT a row order: the default kernels' frozen form (frozen_slab.hip.h freezeSlab, slabSpmvKernel<..., PACKED>) ----
 
 def _hell_of(coo, letter, hack=32, base=0):
     from spgpu_amd import formats

@@ -1,4 +1,4 @@
-"""GPU: the 16-bit copies of frozen matrices AT THEIR LIMITS (include/spgpu/tuning.h Freeze; ellpack_spmv.hip slabPackKernel,
+"""GPU: the 16-bit copies of frozen matrices AT THEIR LIMITS (include/spgpu/tuning.h Freeze; frozen_slab.hip.h slabPackKernel,
 planned_spmv.hip planPackKernel, ragged_spmv.hip.h lens).
 
 A word of the copy is a column's offset from where its group (no row order: the group of rows one wavefront owns, 32 rows for fp32,

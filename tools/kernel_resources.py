@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build-container helper: registers / LDS / scratch of every kernel in one .hip file (device-only compile for gfx950,
-llvm-readelf notes).  usage: tools/kernel_resources.py spgpu_amd/csrc/ellpack_spmv.hip [substring ...]"""
+llvm-readelf notes).  usage: tools/kernel_resources.py spgpu_amd/csrc/ellpack_spmv.hip [substring ...]   (a translation unit, not one of the *.hip.h it includes)"""
 import os
 import re
 import subprocess
