@@ -160,3 +160,147 @@ def test_hell_coo_gives_back_the_triplets(golden_dir, base):
     z1, s1 = X.spmv(n, r, c, v, x, None, 1.5, 0.0, base=base)
     z2, s2 = X.spmv(n, rows, cols, vals, x, None, 1.5, 0.0)
     assert np.max(np.abs(z1 - z2)) <= 1e-15 * np.max(s2) and np.allclose(s1, s2, rtol=1e-15, atol=0)
+
+
+# ---- the Level-1 references ---------------------------------------------------------------------------------------------------
+
+def test_level1_hand_computed_real():
+    x, y, z = np.array([1.0, -2.0, 0.5]), np.array([4.0, 0.25, -8.0]), np.array([10.0, -1.0, 3.0])
+    alpha, beta = 1.5, -0.75
+    cases = {"axpby": ([-1.5, -3.1875, 6.75], [4.5, 3.1875, 6.75]),            # 1.5 x - 0.75 y ; |1.5 x| + |0.75 y|
+             "scal": ([1.5, -3.0, 0.75], [1.5, 3.0, 0.75]),
+             "abs": ([1.5, 3.0, 0.75], [1.5, 3.0, 0.75]),
+             "axy": ([6.0, -0.75, -6.0], [6.0, 0.75, 6.0]),
+             "axypbz": ([-1.5, 0.0, -8.25], [13.5, 1.5, 8.25]),                 # 1.5 x y - 0.75 z
+             "scat": ([-2.0, -2.1875, 6.5], [4.0, 2.1875, 6.5])}               # -0.75 y + x
+    for op, (want, scale) in cases.items():
+        out, s = X.level1(op, "D", alpha, x, y, beta, z)
+        assert out.dtype == np.longdouble and out.astype(np.float64).tolist() == want, op
+        assert s.astype(np.float64).tolist() == scale, op
+
+
+def test_level1_hand_computed_complex():
+    x, y, z = np.array([1 + 2j, -3j]), np.array([2 - 1j, 1 + 1j]), np.array([1j, 4.0])
+    alpha, beta = 2j, 1 - 1j
+    out, s = X.level1("axpby", "Z", alpha, x, y, beta)
+    assert out.dtype == np.clongdouble and out.astype(np.complex128).tolist() == [-4 + 2j - 3j + 1, 6 + 2]
+    np.testing.assert_allclose(s.astype(np.float64), [2 * 5 ** 0.5 + 2 ** 0.5 * 5 ** 0.5, 6 + 2], rtol=1e-15)
+    out, s = X.level1("abs", "C", alpha, np.array([3 + 4j, -5j], np.complex64))
+    assert out.astype(np.complex128).tolist() == [10j, 10j] and s.astype(np.float64).tolist() == [10.0, 10.0]
+    out, s = X.level1("axypbz", "Z", alpha, x, y, beta, z)
+    assert out.astype(np.complex128).tolist() == [2j * (4 + 3j) + (1 - 1j) * 1j, 2j * (3 - 3j) + (1 - 1j) * 4]
+    out, _ = X.level1("axy", "Z", alpha, x, y)
+    assert out.astype(np.complex128).tolist() == [2j * (4 + 3j), 2j * (3 - 3j)]
+    out, _ = X.level1("scat", "Z", 1.0, x, y, beta)
+    assert out.astype(np.complex128).tolist() == [(1 - 1j) * (2 - 1j) + 1 + 2j, (1 - 1j) * (1 + 1j) - 3j]
+
+
+def test_level1_zero_coefficients_leave_operands_unread():
+    """The routes of the reference's dispatch: the operand a route does not read may be NaN or absent."""
+    x, y, z = np.array([1.0, 2.0]), np.array([3.0, 4.0]), np.array([5.0, 6.0])
+    nan = np.full(2, np.nan)
+    assert X.level1_route("axpby", 2.0, 0.0) == "scal" and X.level1_route("axypbz", 0.0, 2.0) == "scal_z"
+    assert X.level1_route("axypbz", 2.0, 0j) == "axy" and X.level1_route("scat", 1.0, 0.0) == "copy"
+    assert X.level1_route("axypbz", 2.0, 1e-300) == "axypbz"
+    assert X.level1("axpby", "D", 2.0, x, nan, 0.0)[0].astype(float).tolist() == [2.0, 4.0]
+    assert X.level1("axpby", "D", 2.0, x, None, 0.0)[0].astype(float).tolist() == [2.0, 4.0]
+    assert X.level1("axypbz", "D", 0.0, nan, nan, 3.0, z)[0].astype(float).tolist() == [15.0, 18.0]
+    assert X.level1("axypbz", "D", 2.0, x, y, 0.0, nan)[0].astype(float).tolist() == [6.0, 16.0]
+    assert X.level1("scat", "D", 1.0, x, nan, 0.0)[0].astype(float).tolist() == [1.0, 2.0]
+    assert np.isnan(X.level1("axypbz", "D", 2.0, x, y, 1.0, nan)[0].astype(float)).all()
+
+
+def test_level1_k_of_each_operation():
+    """The table of level1_k's docstring, spelled out: real / complex, and the shorter trees behind a zero coefficient."""
+    full = {"scal": (1, 2), "abs": (1, 6), "axy": (2, 4), "axpby": (2, 4), "axypbz": (2, 4), "scat": (1, 2)}
+    assert set(full) == set(X.LEVEL1_OPS)
+    for op, (real, cplx) in full.items():
+        for letter in "SD":
+            assert X.level1_k(op, letter, 1.5, -0.75) == real, (op, letter)
+        for letter in "CZ":
+            assert X.level1_k(op, letter, 1.5 - 0.5j, 2j) == cplx, (op, letter)
+    assert X.level1_k("axpby", "D", 1.5, 0.0) == 1 and X.level1_k("axpby", "Z", 1.5, 0.0) == 2
+    assert X.level1_k("axypbz", "S", 0.0, 2.0) == 1 and X.level1_k("axypbz", "C", 0.0, 2.0) == 2
+    assert X.level1_k("axypbz", "S", 2.0, 0.0) == 2 and X.level1_k("axypbz", "C", 2.0, 0.0) == 4
+    assert X.level1_k("scat", "D", 1.0, 0.0) == 0 and X.level1_k("scat", "Z", 1.0, 0.0) == 0
+    assert X.level1_k("abs", "D", 1.0) == 0 and X.level1_k("abs", "Z", 1.0) == 4
+    assert X.EPS["S"] == X.EPS["C"] == 2.0 ** -24 and X.EPS["D"] == X.EPS["Z"] == 2.0 ** -53
+
+
+@pytest.mark.parametrize("letter", ["S", "D", "C", "Z"])
+@pytest.mark.parametrize("op", X.LEVEL1_OPS)
+def test_level1_bound_holds_for_the_rounded_value_and_fails_outside(letter, op):
+    """The long double value rounded once to the type (half an ulp per component, less than any k >= 1 allows; k = 0 is a copy and
+    exact) lies inside the bound; a value k + 1 bounds away does not, and the report names its index.  Chunked with several
+    workers = unchunked."""
+    rng = np.random.default_rng(3)
+    n = 1000
+    dt = X.DTYPE_OF[letter]
+    mk = lambda: (rng.standard_normal(n) + (1j * rng.standard_normal(n) if letter in "CZ" else 0)).astype(dt)
+    x, y, z = mk(), mk(), mk()
+    alpha, beta = (dt(1.5 - 0.5j), dt(-0.75 + 2j)) if letter in "CZ" else (dt(1.5), dt(-0.75))
+    want, scale = X.level1(op, letter, alpha, x, y, beta, z)
+    got = want.astype(dt)                                  # the correctly rounded result: half an ulp per component
+    X.assert_level1(op, letter, got, alpha, x, y, beta, z)
+    whole = X.level1_worst(op, letter, got, alpha, x, y, beta, z)
+    parts = X.level1_worst(op, letter, got, alpha, x, y, beta, z, chunk=7, workers=3)
+    assert whole == parts and whole[0] == 0 and whole[1] <= 0
+    bad = got.copy()
+    k = X.level1_k(op, letter, alpha, beta)
+    bad[617] = dt(want[617] + 2 * (2 * k + 2) * X.EPS[letter] * scale[617])
+    with pytest.raises(AssertionError, match=r"1 of 1000 outside .* worst at 617"):
+        X.assert_level1(op, letter, bad, alpha, x, y, beta, z, chunk=64, workers=2)
+    bad = got.copy()
+    bad[3] = np.nan
+    assert X.level1_worst(op, letter, bad, alpha, x, y, beta, z, chunk=5)[::2] == (1, 3)
+
+
+def test_integer_sums_hand_computed():
+    a, b = np.array([1.0, -2.0, 0.0, 3.0], np.float32), np.array([2.0, 3.0, 5.0, -1.0], np.float32)
+    s = X.integer_sums("S", a, b)
+    assert s == {"nrm2sq": 14, "asum": 6, "amax": 3, "dot": (-7, 0), "dot_terms": 11}
+    c, d = np.array([1 + 2j, -3j], np.complex64), np.array([2 - 1j, 1 + 1j], np.complex64)
+    s = X.integer_sums("C", c, d)                          # un-conjugated: (1+2j)(2-1j) + (-3j)(1+1j) = 4+3j + 3-3j
+    assert s["dot"] == (7, 0) and s["nrm2sq"] == 14 and s["asum"] is None and s["amax"] is None
+    assert s["dot_terms"] == max(2 + 2 + 0 + 3, 1 + 4 + 0 + 3)
+    s = X.integer_sums("Z", np.array([3j, -2.0, 0.0]))
+    assert s["asum"] == 5 and s["amax"] == 3 and s["nrm2sq"] == 13
+    with pytest.raises(AssertionError, match="not integer-valued"):
+        X.integer_sums("D", np.array([0.5]))
+    X.assert_sums_exact("S", {"nrm2sq": (1 << 24) - 1, "asum": None})
+    with pytest.raises(AssertionError, match="nrm2sq"):
+        X.assert_sums_exact("S", {"nrm2sq": 1 << 24})
+    X.assert_sums_exact("D", {"dot_terms": 1 << 24})
+    assert X.rounded_sqrt("S", 14) == np.sqrt(np.float32(14)) and X.rounded_sqrt("D", 14) == 14 ** 0.5
+    assert X.rounded_sqrt("S", 14).dtype == np.float32
+
+
+def test_integer_vectors_are_what_they_say():
+    for letter in "SDCZ":
+        v = X.integer_vector(letter, 5, 100_000, support_seed=9)
+        w = X.integer_vector(letter, 6, 100_000, support_seed=9)
+        assert v.dtype == X.DTYPE_OF[letter] and np.array_equal(v != 0, w != 0) and not np.array_equal(v, w)
+        share = np.count_nonzero(v) / v.size
+        assert 0.02 < share < 0.04 and np.all(v[:8] != 0) and np.all(v[-8:] != 0)
+        comps = np.concatenate([v.real, v.imag]) if letter in "CZ" else v
+        assert set(np.unique(comps)) == {-3, -2, -1, 0, 1, 2, 3}
+    axis = X.integer_vector("C", 7, 100_000, axis_only=True)
+    assert not np.any((axis.real != 0) & (axis.imag != 0)) and np.any(axis.real != 0) and np.any(axis.imag != 0)
+    assert X.integer_density("S", 1000) == 0.03 and X.integer_density("S", 1 << 26) < 0.02 and X.integer_density("D", 1 << 30) == 0.03
+
+
+@pytest.mark.parametrize("letter", ["S", "D", "C", "Z"])
+def test_chosen_integer_inputs_keep_every_partial_sum_exact(letter):
+    """The vectors tests/test_gpu_level1_shapes.py reduces at its two largest sizes (same seeds, same makers): the sum of the
+    magnitudes of the terms of dot, nrm2^2 and asum is below 2^24 / 2^53, and well above zero (a lost tile would show)."""
+    import level1_launch_shapes as shapes
+    sizes = [(*shapes.REDUCE_CAP_SEEDS, shapes.n_past_reduce_cap(letter))] + \
+        ([(*shapes.REDUCE_NT_SEEDS, shapes.n_reduce_nt(letter))] if letter != "Z" else [])
+    for seed, axis_seed, n in sizes:
+        a, b, sums = X.integer_pair(letter, seed, n)          # asserts the condition itself
+        v, vs = X.axis_vector(letter, axis_seed, n)
+        limit = X.EXACT_LIMIT[letter]
+        assert max(sums["nrm2sq"], sums["dot_terms"], vs["asum"]) < limit
+        tiles = n // (shapes.TILE * shapes.WIDE[letter])
+        assert min(sums["nrm2sq"], sums["dot_terms"], vs["asum"]) > 20 * tiles       # tens of terms per tile of 1 024 packs
+        assert sums["dot"] != (0, 0) and a[-1] * b[-1] != 0 and v[-1] != 0            # the tail element counts
