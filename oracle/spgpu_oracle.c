@@ -977,7 +977,9 @@ void orc_isetscal(int first, int last, int base, int val, int* y)
                 T sum = P##_zero();                                                                           \
                 for (int k = 0; k < rS[i]; ++k) {                                                             \
                     const size_t s = slot0 + (size_t)k * (size_t)hackSize;                                    \
-                    sum = P##_fma(cM[s], X[(size_t)(rP[s] - baseIndex) * (size_t)ldX + j], sum);              \
+                    const int col = rP[s] - baseIndex; /* below the base: a hole, skipped as in the SpMV */   \
+                    if (col >= 0)                                                                             \
+                        sum = P##_fma(cM[s], X[(size_t)col * (size_t)ldX + j], sum);                          \
                 }                                                                                             \
                 if (P##_nz(beta))                                                                             \
                     Z[out + j] = P##_fma(beta, Y[out + j], P##_mul(alpha, sum));                              \

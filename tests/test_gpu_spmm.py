@@ -92,6 +92,27 @@ def test_multivector_layout_converters(gpu, letter):
         assert np.array_equal(got[:, j], src[j * pitch:j * pitch + n])
         assert np.array_equal(back.cpu().numpy()[j * pitch:j * pitch + n], src[j * pitch:j * pitch + n])
     assert not np.any(got[:, count:])
+    # the edges of mvTransposeKernel's 32 x 32 tile, both axes: one below, on and one above; ld and pitch larger than needed, and
+    # every element of a destination that is no vector element holds a sentinel before and after
+    sentinel = -7777.25
+    for n in (31, 32, 33):
+        for count in (1, 32, 33):
+            pitch, ld = n + 3, count + 2
+            src = np.full(count * pitch + 5, np.nan, dtype=src.dtype)
+            vec = synth.values_for(letter, 10 + n + count, n * count).reshape(count, n)
+            for j in range(count):
+                src[j * pitch:j * pitch + n] = vec[j]
+            d_src = formats.to_device(src)
+            inter = torch.full((n * ld + 5,), sentinel, dtype=d_src.dtype, device="cuda:0")
+            capi.mv_interleave[letter](gpu, _p(inter), ld, _p(d_src), pitch, n, count)
+            back = torch.full_like(d_src, sentinel)
+            capi.mv_deinterleave[letter](gpu, _p(back), pitch, _p(inter), ld, n, count)
+            torch.cuda.synchronize()
+            want_inter = np.full(n * ld + 5, sentinel, dtype=src.dtype)
+            want_inter[:n * ld].reshape(n, ld)[:, :count] = vec.T
+            assert inter.cpu().numpy().tobytes() == want_inter.tobytes(), (n, count)
+            want_back = np.where(np.isnan(src), src.dtype.type(sentinel), src)
+            assert back.cpu().numpy().tobytes() == want_back.tobytes(), (n, count)
 
 
 @pytest.mark.parametrize("pattern", ["banded", "random"])
