@@ -18,6 +18,10 @@
  * format construction, not the SpMV path); row starts by binary search in the sorted rows; an entry's position k
  * inside its row is its sorted position minus the row's start.  No atomics: the arrays do not depend on scheduling,
  * and a row of any length costs what its entries cost.
+ *
+ * A holder of CSR needs none of this: ext/csr_device.h builds the same ELL and HELL arrays from csrRowPtr / csrColIndices /
+ * csrValues with no sort and no scratch (spgpuCsrRowLengthsDevice, spgpuCsrToEllDevice, spgpuCsrToHellDevice), and takes its
+ * hackOffsets from spgpuHellPlanDevice below, for which `work` of spgpuCooConvertWorkBytes(rowsCount, 0) bytes is enough.
  */
 #include "core.h"
 

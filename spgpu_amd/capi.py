@@ -190,6 +190,20 @@ spgpuCooToHdiaScratchBytes = _decl("spgpuCooToHdiaScratchBytes", C.c_size_t, [i3
 spgpuCooToHdiaDevice = _decl("spgpuCooToHdiaDevice", i32, [Handle, ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, i32, i32, i32, ptr, ptr])
 
 
+# ---- ext/csr_device.h: CSR -> ELL / HELL in HBM, no sort and no scratch --------------------------------------------
+spgpuCsrRowLengthsDevice = _decl("spgpuCsrRowLengthsDevice", i32, [Handle, ptr, C.POINTER(i32), i32, ptr, i32])
+spgpuCsrToEllDevice = _decl("spgpuCsrToEllDevice", i32, [Handle, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, i32, i32, ptr])
+spgpuCsrToHellDevice = _decl("spgpuCsrToHellDevice", i32, [Handle, ptr, ptr, ptr, i32, i32, i32, ptr, ptr, ptr, i32, i32, ptr])
+# not in the headers: the two fills behind the calls above, for the A/B tool and the tests that compare them
+# (..., rIdx, fill, maxBlocks): fill CSR_FILL_PLAIN (one thread per row) or CSR_FILL_TRANSPOSE (a wavefront per 32 rows,
+# CSR_FILL_CHUNK slab columns per trip through LDS); maxBlocks > 0 caps the grid
+CSR_FILL_PLAIN, CSR_FILL_TRANSPOSE = 0, 1
+spgpuCsrToEllDeviceWith = _bind("spgpuCsrToEllDeviceWith", i32, spgpuCsrToEllDevice.argtypes + [i32, i32])
+spgpuCsrToHellDeviceWith = _bind("spgpuCsrToHellDeviceWith", i32, spgpuCsrToHellDevice.argtypes + [i32, i32])
+CSR_FILL_CHUNK = _bind("spgpuCsrFillChunk", i32, [])()
+CSR_FILL_DEFAULT = _bind("spgpuCsrDefaultFill", i32, [])()
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -113,6 +113,17 @@ def random_rows_coo(n_rows, n_cols, lengths, seed=1, letter="D", base=0, shuffle
     return n_rows, n_cols, (rows + base).astype(np.int32), (cols + base).astype(np.int32), vals
 
 
+def coo_to_csr(n_rows, rows, cols, vals, base=0):
+    """CSR arrays (row_ptr int32 of n_rows + 1 entries starting at `base`, cols, vals) of COO triplets whose row indices are in
+    `base`, in any entry order: a STABLE sort by row, so the k-th CSR entry of a row is its k-th occurrence in the COO order
+    (what the COO converters store as the row's k-th entry); duplicates are kept, the columns keep their base."""
+    rows = np.asarray(rows, dtype=np.int64) - base
+    order = np.argsort(rows, kind="stable")
+    row_ptr = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n_rows)[:n_rows], out=row_ptr[1:])
+    return (row_ptr + base).astype(np.int32), np.ascontiguousarray(np.asarray(cols)[order], dtype=np.int32), np.ascontiguousarray(np.asarray(vals)[order])
+
+
 def banded_coo(n, half_width=16, letter="D", seed=2, base=0):
     """n x n band: row i has columns i-half_width .. i+half_width-1 clipped to [0, n)."""
     i = np.arange(n, dtype=np.int64)[:, None]
