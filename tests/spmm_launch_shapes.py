@@ -1,32 +1,33 @@
-"""The constants of the SpMM dispatch (spgpu_amd/csrc/hell_spmm.hip), both dispatches restated as a function of what a caller
-passes, and the matrices tests/test_gpu_spmm_shapes.py runs them on, stated once for that module (which runs them on the GPU) and
+"""The constants of the SpMM dispatch (spgpu_amd/csrc/hell_spmm.hip; kernels in spmm_rows.hip.h and spmm_strip.hip.h), both
+dispatches restated as a function of what a caller passes, and the matrices tests/test_gpu_spmm_shapes.py runs them on, stated once for that module (which runs them on the GPU) and
 for tests/test_spmm_launch_shapes.py (which checks on the CPU that the matrices have the windows each kernel branch needs and that
 the case table names every instantiation).  No torch, no library: importable everywhere."""
 import numpy as np
 
-# ---- the constants of the dispatch, with the line that sets each: a change there is a test to revisit here -------------------
-PASS = 16                     # hell_spmm.hip:1081, 1149   right-hand sides of one pass
-THREADS = 256                 # hell_spmm.hip:65     kSpmmThreads: 256 rows per workgroup
+# ---- the constants of the dispatch, with the name that sets each: a change there is a test to revisit here -------------------
+PASS = 16                     # kSpmmPass: right-hand sides of one pass
+THREADS = 256                 # kSpmmThreads: 256 rows per workgroup
 WAVE = 64                     # rows per wavefront
-SPMM_TILE_BYTES = 43 * 1024   # hell_spmm.hip:66     kSpmmTileBytes (the tiled one-row-per-lane kernel)
-STRIP_TILE_BYTES = 40 * 1024  # hell_spmm.hip:491    kStripTileBytes (the strip kernel)
-SLAB_HEAD = 32                # hell_spmm.hip:728    kStageCols * HEAD: slab columns whose indices the strip kernel keeps in registers
+SPMM_TILE_BYTES = 43 * 1024   # kSpmmTileBytes (the tiled one-row-per-lane kernel)
+STRIP_TILE_BYTES = 40 * 1024  # kStripTileBytes (the strip kernel)
+SLAB_HEAD = 32                # kStageCols * HEAD (hellSpmmStripKernel): slab columns whose indices the strip kernel keeps in registers
 SIZEOF = {"S": 4, "D": 8}
 CTYPE = {"S": "float", "D": "double"}
 
 
 def strip_tile_rows(letter, vec):
-    """launchSpmmStrips, hell_spmm.hip:1049"""
+    """launchSpmmStrips<T, TRIP, VEC>: a.tileRows"""
     return STRIP_TILE_BYTES // (8 * vec * SIZEOF[letter])
 
 
 def tiled_tile_rows(letter, kp=8, vec=2):
-    """launchSpmm<T, 8, 2, 4, true>, hell_spmm.hip:1063"""
+    """launchSpmm<T, 8, 2, 4, true>: a.tileRows"""
     return SPMM_TILE_BYTES // (kp * vec * SIZEOF[letter])
 
 
 def mv_strip_tile_rows(letter, vec):
-    """hellSpmmMv, hell_spmm.hip:1173-1178: the window's low end is rounded down to a 16-byte piece, `round` rows are kept free"""
+    """launchSpmmStrips<T, TRIP, VEC, true>: the window's low end is rounded down to a 16-byte piece, the rows that costs
+    are kept free"""
     return STRIP_TILE_BYTES // (8 * vec * SIZEOF[letter]) - (16 // SIZEOF[letter] - 1)
 
 
@@ -47,7 +48,8 @@ ALIGNED = dict(cM=0, rP=0, X=0, Y=0, Z=0)
 
 
 def interleaved_passes(letter, hack, count, ldx, ldyz, r_idx=False, off=ALIGNED, has_y=True):
-    """hellSpmm (hell_spmm.hip:1068-1132) restated.  `off`: bytes by which cM, rP, X, Y, Z lie past a 16-byte boundary.
+    """hellSpmm<T, false> restated: matrixLoads16, spmmShape (enum SpmmShape) and launchSpmmStrips' directFill.  `off`: bytes by
+    which cM, rP, X, Y, Z lie past a 16-byte boundary.
     Returns, per pass of 16, (kernel name as the profiler prints it, directFill) -- directFill is None off the strip kernel.
     r_idx changes no choice of this call; it is an argument so that both dispatches take the same ones."""
     size = SIZEOF[letter]
@@ -88,7 +90,7 @@ def interleaved_passes(letter, hack, count, ldx, ldyz, r_idx=False, off=ALIGNED,
 
 
 def mv_passes(letter, hack, count, pitch_x, pitch_yz, r_idx=False, off=ALIGNED, has_y=True):
-    """hellSpmmMv (hell_spmm.hip:1138-1186) restated: per pass, (kernel name, wideRuns)."""
+    """hellSpmm<T, true> restated (matrixLoads16, spmmMvShape, a.wideRuns): per pass, (kernel name, wideRuns)."""
     size = SIZEOF[letter]
     matrix16 = hack % 32 == 0 and off["cM"] % 16 == 0 and off["rP"] % 16 == 0
     out = []
@@ -261,8 +263,8 @@ def offsets(letter, shift):
 
 
 def interleaved_cases(letter):
-    """The table of the issue: id -> case.  `want` is a tuple of (short kernel tag, directFill) per pass; tags: strip2, strip1,
-    tiled, k16, k4x2, k8x1, k4x1."""
+    """The table of the issue: id -> case.  `want` is a tuple of (short kernel tag, directFill) per pass; the tags are the members
+    of enum SpmmShape: strip2, strip1, tiled, k16, k4x2, k8x1, k4x1."""
     c = {}
     # strip kernel, two per lane, directFill on
     for hack in (32, 64, 96):
@@ -276,7 +278,7 @@ def interleaved_cases(letter):
     # strip kernel, one per lane, directFill on
     c["strip1-direct-count8"] = case(8, want=(("strip1", True),))
     # count 4 with ldX = 4: the strip kernel with half of each team idle; directFill needs all 8 right-hand sides
-    # (hell_spmm.hip:1051), so it is off here for both types
+    # (launchSpmmStrips), so it is off here for both types
     c["strip1-count4-ld4"] = case(4, want=(("strip1", False),))
     # the same, directFill off
     c["strip1-count5"] = case(5, ldx=6, want=(("strip1", False),))

@@ -284,8 +284,8 @@ def test_spmm_hack_sizes_off_the_strip_path(gpu, letter, hs):
 @pytest.mark.parametrize("letter", ["D", "S"])
 def test_band_wavefronts_and_their_neighbours(gpu, letter):
     """Round 4: wavefronts whose 64 rows form a band through all their columns take the sliding-window loop of the strip kernel
-    (hell_spmm.hip, BAND).  The banded test matrix wraps its columns at both ends, so its first and last wavefronts are NOT bands and
-    run the general loop beside band wavefronts of the same workgroup; then a matrix with scattered columns is copied over the same
+    (bandBase in hellSpmmStripKernel, spmm_strip.hip.h).  The banded test matrix wraps its columns at both ends, so its first and last
+    wavefronts are NOT bands and run the general loop beside band wavefronts of the same workgroup; then a matrix with scattered columns is copied over the same
     arrays (no wavefront qualifies).  Every call: the oracle's bits (beta != 0, 16 right-hand sides)."""
     import torch
     from spgpu_amd import capi, synth

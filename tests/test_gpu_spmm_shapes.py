@@ -1,4 +1,4 @@
-"""GPU: spgpu?hellspmm and spgpu?hellspmmMv on every kernel instantiation their dispatches can choose (hell_spmm.hip:1068-1186) and
+"""GPU: spgpu?hellspmm and spgpu?hellspmmMv on every kernel instantiation their dispatches can choose (hellSpmm, hell_spmm.hip) and
 on the workgroup-uniform branches inside the kernels that no argument names: window fits the LDS tile or not, decided at the probe
 or after the scan, a workgroup without entries, direct or staged tile fill, 16-byte runs or single elements in the pitch layout,
 wavefronts of uniform rows, band wavefronts.  The constants, both dispatches restated, the case tables and the 613-row matrices
@@ -255,7 +255,7 @@ def test_in_place_sum_on_every_instantiation(gpu, letter, cid):
 @pytest.mark.parametrize("letter", "SD")
 def test_nan_in_row_0_of_x_reaches_nothing(gpu, letter, cid, base):
     """Absent entries -- past a row's length, and the holes of the 1-based matrix -- read row 0 of X and discard the product
-    (hell_spmm.hip:231).  The matrix names column 0 nowhere, row 0 of X holds NaN: none may reach Z."""
+    (spmmAccumulate's global-memory loop, spmm_rows.hip.h).  The matrix names column 0 nowhere, row 0 of X holds NaN: none may reach Z."""
     c = S.interleaved_cases(letter)[cid]
     Xk = _operands(letter, c["count"])[0].copy()
     Xk[0] = np.nan

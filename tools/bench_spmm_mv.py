@@ -2,7 +2,7 @@
 """A/B of the HELL SpMM for a caller who holds the reference's multivector layout (vector j at base + j*pitch).
 
 One process, one set of allocations, the matrices of bench.py's SpMM leg (synth.hell_uniform_on_device, fp64, 5 M rows x 32,
-hackSize 32), the vectors in the pitch layout with pitch = rows.  Three routes:
+hackSize --hack, default 32), the vectors in the pitch layout with pitch = rows.  Three routes:
 
   a  spgpuDhellspmmMv                                                   (include/spgpu/ext/spmm_mv.h)
   b  mvInterleave(X) [+ mvInterleave(Y)] -> spgpuDhellspmm -> mvDeinterleave(Z)     what such a caller had before
@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--nnz-per-row", type=int, default=32)
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--routes", default="a,b,c")
+    ap.add_argument("--hack", type=int, default=32, help="hackSize of the matrices (a multiple of 32 reaches the strip kernels)")
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--block-ms", type=float, default=60.0, help="device time a block aims at (5 to 100 calls)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spmm_mv_ab.json"))
@@ -57,7 +58,7 @@ def main():
     from spgpu_amd import capi, synth
     assert torch.cuda.is_available(), "bench_spmm_mv.py measures on the GPU; there is none"
     h = capi.create_handle(0)
-    n, L, hack = args.rows, args.nnz_per_row, 32
+    n, L, hack = args.rows, args.nnz_per_row, args.hack
     routes = args.routes.split(",")
     kmax = max(CASES[c][1] for c in args.cases.split(","))
     Xp, Yp = synth.device_vector(n * kmax, "D", 3), synth.device_vector(n * kmax, "D", 4)   # pitch layout, pitch = n
