@@ -10,6 +10,7 @@
  * 0 <= offsets[d] + r < cols.  z may alias y exactly; calls are asynchronous on
  * handle->currentStream.  On MI355X this is the HDIA kernel run over one
  * all-rows hack (the addressing is identical with hackSize = dMPitch).
+ * Several vectors at once (vector j at base + j*pitch): spgpu?diaspmmMv, spgpu/ext/hdia_spmm.h.
  */
 #include "core.h"
 

@@ -13,6 +13,7 @@
  *     dM[d*hackSize + r%hackSize]   = coefficient of row r on it
  *   A stored slot contributes iff 0 <= offsets[d] + r < cols.
  * z may alias y exactly.  Calls are asynchronous on handle->currentStream.
+ * Several vectors at once (vector j at base + j*pitch): spgpu?hdiaspmmMv, spgpu/ext/hdia_spmm.h.
  */
 #include "core.h"
 

@@ -149,6 +149,16 @@ for _L in "SD":
     hellspmm_mv[_L] = _decl(f"spgpu{_L}hellspmmMv", None,
                             [Handle, ptr, ptr, _T, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, ptr, _T, i32, i32, i32, i32])
 
+# ---- ext/hdia_spmm.h: the HDIA and DIA SpMM on the same layout: spgpu?hdiaspmv's / spgpu?diaspmv's arguments, then
+# count, pitchX, pitchYZ ----------
+hdiaspmm_mv, diaspmm_mv = {}, {}
+for _L in "SD":
+    _T = SCALAR[_L]
+    hdiaspmm_mv[_L] = _decl(f"spgpu{_L}hdiaspmmMv", None,
+                            [Handle, ptr, ptr, _T, ptr, ptr, i32, ptr, i32, i32, ptr, _T, i32, i32, i32])
+    diaspmm_mv[_L] = _decl(f"spgpu{_L}diaspmmMv", None,
+                           [Handle, ptr, ptr, _T, ptr, ptr, i32, i32, i32, i32, ptr, _T, i32, i32, i32])
+
 # ---- ell_conv.h / hell_conv.h / hdia_conv.h (host pointers) --------------------------
 computeEllRowLenghts = _decl("computeEllRowLenghts", None, [ptr, C.POINTER(i32), i32, i32, ptr, i32])
 computeEllAllocPitch = _decl("computeEllAllocPitch", i32, [i32])
