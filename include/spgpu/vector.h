@@ -13,6 +13,9 @@
  * Reductions use scratch owned by the handle (the reference uses one
  * process-global device array, kernels/ddot.cu:35), so two handles may run
  * them concurrently; a single handle must not be shared between host threads.
+ * Results and coefficients in device memory, without the synchronisation:
+ * spgpu/device_scalars.h (one vector) and spgpu/ext/device_scalars_mv.h
+ * (multivectors, one result / coefficient per vector; S and D).
  */
 #include "core.h"
 

@@ -282,6 +282,20 @@ for _L in "SD":
                                       [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr])
 
 
+# ---- ext/device_scalars_mv.h: the same on pitch multivectors, one result / coefficient per vector (arrays of `count` elements);
+# count and pitch follow the single-vector argument list ----------
+mdot_device, mnrm2_device, mdiv_device = {}, {}, {}
+maxpby_device, maxpby_quot_device, maxpby_pair_dot_device = {}, {}, {}
+for _L in "SD":
+    mdot_device[_L] = _decl(f"spgpu{_L}mdotDevice", None, [Handle, ptr, i32, ptr, ptr, i32, i32])
+    mnrm2_device[_L] = _decl(f"spgpu{_L}mnrm2Device", None, [Handle, ptr, i32, ptr, i32, i32])
+    mdiv_device[_L] = _decl(f"spgpu{_L}mdivDevice", None, [Handle, ptr, ptr, ptr, i32, i32])
+    maxpby_device[_L] = _decl(f"spgpu{_L}maxpbyDevice", None, [Handle, ptr, i32, ptr, ptr, ptr, ptr, i32, i32])
+    maxpby_quot_device[_L] = _decl(f"spgpu{_L}maxpbyQuotDevice", None,
+                                   [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, i32, ptr, i32, i32])
+    maxpby_pair_dot_device[_L] = _decl(f"spgpu{_L}maxpbyPairDotDevice", None,
+                                       [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
+
 # ---- tuning.h: per-handle kernel-form hint ---------------------------------------------------------------------
 FORM_AUTO, FORM_GATHER, FORM_STRIPS, FORM_XTILE, FORM_SWEEP = range(5)
 spgpuSetSpmvForm = _decl("spgpuSetSpmvForm", None, [Handle, i32])

@@ -1,7 +1,8 @@
 /*
  * Fused steps of a Krylov iteration on small systems, for gfx950 (MI355X).
  *
- * C ABI: spgpu{S,D}hellspmvDotDevice, spgpu{S,D}axpbyPairDotDevice (include/spgpu/device_scalars.h).  NEW: the
+ * C ABI: spgpu{S,D}hellspmvDotDevice, spgpu{S,D}axpbyPairDotDevice (include/spgpu/device_scalars.h) and
+ * spgpu{S,D}maxpbyPairDotDevice (include/spgpu/ext/device_scalars_mv.h).  NEW: the
  * reference has no fused calls; a CG iteration written with it is hellspmv + dot + 2 axpby + dot + axpby, each
  * reduction a host round trip (vector.h:61-120, ddot.cu:120-150).  On the 1024 x 1024 Laplacian (BASELINE
  * configs[0]) every one of those kernels moves 8-60 MB that sit in the Infinity Cache: the iteration is bound by
@@ -24,6 +25,7 @@
 #include "reduce.hip.h"
 
 #include "spgpu/device_scalars.h"
+#include "spgpu/ext/device_scalars_mv.h"
 
 #include <stdint.h>
 
@@ -239,12 +241,9 @@ static void hellSpmvDot(spgpuHandle_t handle, T* result, const T* w, T* z, const
 /* z1 = y1 + a*x1, z2 = y2 - a*x2, partial sums of z2 . z2; a = *alphaNum / *alphaDen.
  * Arithmetic of axpbyDeviceKernel with beta = 1 (level1.hip): fma(a, x, 1*y) and fma(-a, x, 1*y). */
 template <typename T, int VEC>
-__global__ __launch_bounds__(kL1Threads) void axpbyPairDotKernel(T* partials, int n, T* z1, const T* y1, const T* x1, T* z2,
-                                                                const T* y2, const T* x2, const T* alphaNum,
-                                                                const T* alphaDen)
+__device__ inline T axpbyPairDotBlock(int n, T* z1, const T* y1, const T* x1, T* z2, const T* y2, const T* x2, T up, T* lds)
 {
-    __shared__ T lds[kL1Threads / kWave];
-    const T up = quotientAt(alphaNum, alphaDen), down = -up, one = T(1);
+    const T down = -up, one = T(1);
     T acc = zeroOf<T>();
     const long long packs = n / VEC;
     constexpr long long TILE = (long long)kL1Threads * kL1Unroll;
@@ -285,9 +284,33 @@ __global__ __launch_bounds__(kL1Threads) void axpbyPairDotKernel(T* partials, in
         z2[tail] = o2;
         acc = mulAdd(o2, o2, acc);
     }
-    const T total = blockCombine<kDot>(acc, lds);
+    return blockCombine<kDot>(acc, lds);
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(kL1Threads) void axpbyPairDotKernel(T* partials, int n, T* z1, const T* y1, const T* x1, T* z2,
+                                                                const T* y2, const T* x2, const T* alphaNum,
+                                                                const T* alphaDen)
+{
+    __shared__ T lds[kL1Threads / kWave];
+    const T total = axpbyPairDotBlock<T, VEC>(n, z1, y1, x1, z2, y2, x2, quotientAt(alphaNum, alphaDen), lds);
     if (threadIdx.x == 0)
         partials[blockIdx.x] = total;
+}
+
+/* The same on the vectors of a pitch multivector (spgpu/ext/device_scalars_mv.h): grid (blocks, vectors) of the first stage of
+ * spgpu?mdotDevice(result, n, z2, z2, count, pitch); vector blockIdx.y takes element blockIdx.y of alphaNum / alphaDen. */
+template <typename T, int VEC>
+__global__ __launch_bounds__(kL1Threads) void axpbyPairDotMvKernel(T* partials, int n, T* z1, const T* y1, const T* x1, T* z2,
+                                                                  const T* y2, const T* x2, const T* alphaNum,
+                                                                  const T* alphaDen, long long pitch)
+{
+    __shared__ T lds[kL1Threads / kWave];
+    const long long shift = (long long)blockIdx.y * pitch;
+    const T up = quotientAt(alphaNum ? alphaNum + blockIdx.y : nullptr, alphaDen ? alphaDen + blockIdx.y : nullptr);
+    const T total = axpbyPairDotBlock<T, VEC>(n, z1 + shift, y1 + shift, x1 + shift, z2 + shift, y2 + shift, x2 + shift, up, lds);
+    if (threadIdx.x == 0)
+        partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 template <typename T>
@@ -310,6 +333,39 @@ static void axpbyPairDot(spgpuHandle_t handle, T* result, int n, T* z1, const T*
     }
     hipLaunchKernelGGL((reduceFinalKernel<T, kDot>), dim3(1), dim3(kWave), 0, s, result, partials, (int)blocks);
     spgpuDebugCheck(handle, "axpbyPairDotDevice");
+}
+
+/* Passes, grid and `wide` of spgpu?mdotDevice on (z2, z2) (level1.hip reduceVectorsToDevice), the first stage replaced. */
+template <typename T>
+static void axpbyPairDotMv(spgpuHandle_t handle, T* result, int n, T* z1, const T* y1, const T* x1, T* z2, const T* y2,
+                           const T* x2, const T* alphaNum, const T* alphaDen, int count, int pitch)
+{
+    if (count <= 0)
+        return;
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    hipStream_t s = handle->currentStream;
+    T* partials = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
+    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
+        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
+        const size_t shift = (size_t)first * pitch;
+        long long blocks = 0;
+        if (n > 0) {
+            const bool wide = reduceWide<T>(z2 + shift, z2 + shift, vectors, pitch);
+            blocks = reduceBlocks<T>(n, wide, vectors);
+            const dim3 grid((unsigned)blocks, (unsigned)vectors);
+            const T* num = alphaNum ? alphaNum + first : nullptr;
+            const T* den = alphaDen ? alphaDen + first : nullptr;
+            if (wide)
+                hipLaunchKernelGGL((axpbyPairDotMvKernel<T, WIDE>), grid, dim3(kL1Threads), 0, s, partials, n, z1 + shift,
+                                   y1 + shift, x1 + shift, z2 + shift, y2 + shift, x2 + shift, num, den, (long long)pitch);
+            else
+                hipLaunchKernelGGL((axpbyPairDotMvKernel<T, 1>), grid, dim3(kL1Threads), 0, s, partials, n, z1 + shift,
+                                   y1 + shift, x1 + shift, z2 + shift, y2 + shift, x2 + shift, num, den, (long long)pitch);
+        }
+        hipLaunchKernelGGL((reduceFinalBatchKernel<T, kDot>), dim3((unsigned)vectors), dim3(kWave), 0, s, result + first,
+                           partials, (int)blocks);
+    }
+    spgpuDebugCheck(handle, "maxpbyPairDotDevice");
 }
 
 } // namespace spgpu
@@ -335,6 +391,15 @@ void spgpuSaxpbyPairDotDevice(spgpuHandle_t h, float* result, int n, float* z1, 
 void spgpuDaxpbyPairDotDevice(spgpuHandle_t h, double* result, int n, double* z1, const double* y1, const double* x1,
                               double* z2, const double* y2, const double* x2, const double* alphaNum, const double* alphaDen)
 { axpbyPairDot<double>(h, result, n, z1, y1, x1, z2, y2, x2, alphaNum, alphaDen); }
+
+void spgpuSmaxpbyPairDotDevice(spgpuHandle_t h, float* result, int n, float* z1, const float* y1, const float* x1, float* z2,
+                               const float* y2, const float* x2, const float* alphaNum, const float* alphaDen, int count, int pitch)
+{ axpbyPairDotMv<float>(h, result, n, z1, y1, x1, z2, y2, x2, alphaNum, alphaDen, count, pitch); }
+
+void spgpuDmaxpbyPairDotDevice(spgpuHandle_t h, double* result, int n, double* z1, const double* y1, const double* x1,
+                               double* z2, const double* y2, const double* x2, const double* alphaNum, const double* alphaDen,
+                               int count, int pitch)
+{ axpbyPairDotMv<double>(h, result, n, z1, y1, x1, z2, y2, x2, alphaNum, alphaDen, count, pitch); }
 
 } // extern "C"
 

@@ -6,7 +6,9 @@
  *        asum, amax (+m forms)
  *        (include/spgpu/vector.h; reference vector.h, kernels/{s,d,c,z}axpby.cu, {s,d,c,z}dot.cu,
  *         {s,d,c,z}nrm2.cu, scal_base.cuh, abs_base.cuh, axy_base.cuh, gath_base.cuh, scat_base.cuh,
- *         setscal_base.cuh, asum_base.cuh, amax_base.cuh).
+ *         setscal_base.cuh, asum_base.cuh, amax_base.cuh);
+ *        results and coefficients in device memory (NEW): include/spgpu/device_scalars.h for one vector,
+ *        include/spgpu/ext/device_scalars_mv.h for pitch multivectors (one result / coefficient per vector).
  *
  * axpby is a pure stream (2 reads + 1 write per element, 1 read when beta==0):
  * 16-byte accesses per lane, a capped grid with a grid-stride loop, one launch
@@ -24,6 +26,7 @@
 
 #include "spgpu/vector.h"
 #include "spgpu/device_scalars.h"
+#include "spgpu/ext/device_scalars_mv.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -122,6 +125,37 @@ __global__ void divDeviceKernel(T* out, const T* num, const T* den, int negate)
 {
     const T q = *num / *den;
     *out = negate ? -q : q;
+}
+
+/* The same on a pitch multivector (spgpu/ext/device_scalars_mv.h): grid.y = vector, element blockIdx.y of every scalar array is
+ * that vector's.  A workgroup loads its vector's coefficients once and takes the body its beta asks for. */
+template <typename T> static inline const T* scalarAt(const T* array, int first) { return array ? array + first : nullptr; }
+template <typename T> __device__ inline const T* scalarOf(const T* array, unsigned vector) { return array ? array + vector : nullptr; }
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(kL1Threads) void axpbyDeviceMvKernel(T* z, int n, int hasBeta, const T* betaNum, const T* betaDen,
+                                                                 const T* y, const T* alphaNum, const T* alphaDen,
+                                                                 int negateAlpha, const T* x, long long pitch)
+{
+    const unsigned j = blockIdx.y;
+    T alpha = quotientAt(scalarOf(alphaNum, j), scalarOf(alphaDen, j));
+    if (negateAlpha)
+        alpha = -alpha;
+    const T beta = hasBeta ? quotientAt(scalarOf(betaNum, j), scalarOf(betaDen, j)) : zeroOf<T>();
+    if (isNotZero(beta))
+        axpbyBody<T, VEC, true>(z, n, beta, y, alpha, x, pitch);
+    else
+        axpbyBody<T, VEC, false>(z, n, beta, y, alpha, x, pitch);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kL1Threads) void divDeviceMvKernel(T* out, const T* num, const T* den, int negate, int count)
+{
+    const unsigned j = blockIdx.x * kL1Threads + threadIdx.x;
+    if (j < (unsigned)count) {
+        const T q = quotientAt(scalarOf(num, j), scalarOf(den, j));
+        out[j] = negate ? -q : q;
+    }
 }
 
 template <typename T, typename ApiT>
@@ -277,6 +311,31 @@ __global__ __launch_bounds__(kL1Threads) void reduceKernel(typename AccOf<T, MOD
 
 }
 
+/* First stage for one pass of `vectors` vectors (at most kReduceMaxVectorsPerPass) that start at a0 / b0: block partials go to
+ * dev[j * blocks + block].  Returns blocks.  The one place that chooses kernel and grid for spgpu?mdot and for every call that
+ * must repeat its bits (spgpu?mdotDevice, spgpu?mnrm2Device). */
+template <typename T, int MODE>
+static long long reduceFirstStage(hipStream_t s, typename AccOf<T, MODE>::type* dev, int n, const T* a0, const T* b0, int vectors,
+                                  int pitch)
+{
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    const bool wide = reduceWide(a0, b0, vectors, pitch);
+    const long long blocks = reduceBlocks<T>(n, wide, vectors);
+    const dim3 grid((unsigned)blocks, (unsigned)vectors);
+
+    const long long streamed = (long long)n * (long long)sizeof(T) * vectors * (MODE == kDot ? 2 : 1);
+    if (wide && streamed >= (256ll << 20))
+        hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE, true>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
+                           (long long)pitch);
+    else if (wide)
+        hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
+                           (long long)pitch);
+    else
+        hipLaunchKernelGGL((reduceKernel<T, 1, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
+                           (long long)pitch);
+    return blocks;
+}
+
 /* Runs the two-stage reduction for `count` vectors and leaves one host value
  * per vector in out[].  Synchronises handle->currentStream. */
 template <typename T, int MODE>
@@ -294,32 +353,11 @@ static void reduceVectors(spgpuHandle_t handle, typename AccOf<T, MODE>::type* o
     Acc* dev = static_cast<Acc*>(priv->reduceScratch);
     Acc* host = static_cast<Acc*>(priv->reduceHost);
 
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const int maxVectorsPerPass = SPGPU_REDUCE_MAX_BLOCKS;
-
-    for (int first = 0; first < count; first += maxVectorsPerPass) {
-        const int vectors = count - first < maxVectorsPerPass ? count - first : maxVectorsPerPass;
+    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
+        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
         const T* a0 = a + (size_t)first * pitch;
         const T* b0 = MODE == kDot ? b + (size_t)first * pitch : nullptr;
-        const bool wide = WIDE > 1 && ((uintptr_t)a0 % 16 == 0) && (MODE != kDot || (uintptr_t)b0 % 16 == 0) &&
-                          (vectors == 1 || pitch % WIDE == 0);
-        const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-        long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-        const long long cap = SPGPU_REDUCE_MAX_BLOCKS / vectors;
-        if (blocks > cap)
-            blocks = cap;
-        const dim3 grid((unsigned)blocks, (unsigned)vectors);
-
-        const long long streamed = (long long)n * (long long)sizeof(T) * vectors * (MODE == kDot ? 2 : 1);
-        if (wide && streamed >= (256ll << 20))
-            hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE, true>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                               (long long)pitch);
-        else if (wide)
-            hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                               (long long)pitch);
-        else
-            hipLaunchKernelGGL((reduceKernel<T, 1, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                               (long long)pitch);
+        const long long blocks = reduceFirstStage<T, MODE>(s, dev, n, a0, b0, vectors, pitch);
         hipError_t status = hipMemcpyAsync(host, dev, sizeof(Acc) * (size_t)blocks * vectors, hipMemcpyDeviceToHost, s);
         if (status == hipSuccess)
             status = hipStreamSynchronize(s);
@@ -389,6 +427,28 @@ static void nrm2ToDevice(spgpuHandle_t handle, T* result, int n, const T* a)
     spgpuDebugCheck(handle, "nrm2Device");
 }
 
+/* dot / nrm2 of a pitch multivector with one result per vector left in device memory (spgpu/ext/device_scalars_mv.h):
+ * the passes and the first stage of reduceVectors, then one wavefront per vector in the order of finalOrder.  A pass reuses the
+ * scratch of the pass before it; stream order keeps them apart. */
+template <typename T, int MODE>
+static void reduceVectorsToDevice(spgpuHandle_t handle, T* result, int n, const T* a, const T* b, int count, int pitch)
+{
+    if (count <= 0)
+        return;
+    hipStream_t s = handle->currentStream;
+    T* dev = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
+    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
+        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
+        long long blocks = 0; /* n <= 0: no first stage, every result of the pass is +0 */
+        if (n > 0)
+            blocks = reduceFirstStage<T, MODE>(s, dev, n, a + (size_t)first * pitch,
+                                               MODE == kDot ? b + (size_t)first * pitch : nullptr, vectors, pitch);
+        hipLaunchKernelGGL((reduceFinalBatchKernel<T, MODE, MODE == kNrm2>), dim3((unsigned)vectors), dim3(kWave), 0, s,
+                           result + first, dev, (int)blocks);
+    }
+    spgpuDebugCheck(handle, "multivector reduction to device");
+}
+
 template <typename T>
 static void axpbyFromDevice(spgpuHandle_t handle, T* z, int n, int hasBeta, const T* betaNum, const T* betaDen, const T* y,
                             const T* alphaNum, const T* alphaDen, int negateAlpha, const T* x)
@@ -410,6 +470,49 @@ static void axpbyFromDevice(spgpuHandle_t handle, T* z, int n, int hasBeta, cons
         hipLaunchKernelGGL((axpbyDeviceKernel<T, 1>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, z, n, hasBeta, betaNum,
                            betaDen, y, alphaNum, alphaDen, negateAlpha, x);
     spgpuDebugCheck(handle, "axpbyDevice");
+}
+
+/* The update of a pitch multivector with per-vector coefficients: the grid of spgpu?maxpby (kL1MaxBlocks shared by the vectors
+ * of a pass). */
+template <typename T>
+static void axpbyFromDeviceMv(spgpuHandle_t handle, T* z, int n, int hasBeta, const T* betaNum, const T* betaDen, const T* y,
+                              const T* alphaNum, const T* alphaDen, int negateAlpha, const T* x, int count, int pitch)
+{
+    if (n <= 0 || count <= 0)
+        return;
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    /* which vectors read y is known on the device only; its alignment is required whenever it is given */
+    const bool wide = ((uintptr_t)z % 16 == 0) && ((uintptr_t)x % 16 == 0) && (!hasBeta || !y || (uintptr_t)y % 16 == 0) &&
+                      (count == 1 || pitch % WIDE == 0);
+    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
+    hipStream_t s = handle->currentStream;
+    for (int first = 0; first < count; first += kL1MaxBlocks) {
+        const int vectors = count - first < kL1MaxBlocks ? count - first : kL1MaxBlocks;
+        long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
+        if (blocks > kL1MaxBlocks / vectors)
+            blocks = kL1MaxBlocks / vectors;
+        const dim3 grid((unsigned)blocks, (unsigned)vectors);
+        const size_t shift = (size_t)first * pitch;
+        if (wide)
+            hipLaunchKernelGGL((axpbyDeviceMvKernel<T, WIDE>), grid, dim3(kL1Threads), 0, s, z + shift, n, hasBeta,
+                               scalarAt(betaNum, first), scalarAt(betaDen, first), y ? y + shift : y, scalarAt(alphaNum, first),
+                               scalarAt(alphaDen, first), negateAlpha, x + shift, (long long)pitch);
+        else
+            hipLaunchKernelGGL((axpbyDeviceMvKernel<T, 1>), grid, dim3(kL1Threads), 0, s, z + shift, n, hasBeta,
+                               scalarAt(betaNum, first), scalarAt(betaDen, first), y ? y + shift : y, scalarAt(alphaNum, first),
+                               scalarAt(alphaDen, first), negateAlpha, x + shift, (long long)pitch);
+    }
+    spgpuDebugCheck(handle, "maxpbyDevice");
+}
+
+template <typename T>
+static void divFromDeviceMv(spgpuHandle_t handle, T* out, const T* num, const T* den, int negate, int count)
+{
+    if (count <= 0)
+        return;
+    hipLaunchKernelGGL(divDeviceMvKernel<T>, dim3((unsigned)((count + kL1Threads - 1) / kL1Threads)), dim3(kL1Threads), 0,
+                       handle->currentStream, out, num, den, negate, count);
+    spgpuDebugCheck(handle, "mdivDevice");
 }
 
 /* ---- element-wise maps: scal, abs, axy, axypbz -------------------------------
@@ -757,4 +860,23 @@ void spgpuSdivDevice(spgpuHandle_t h, float* out, const float* num, const float*
 { hipLaunchKernelGGL(divDeviceKernel<float>, dim3(1), dim3(1), 0, h->currentStream, out, num, den, negate); }
 void spgpuDdivDevice(spgpuHandle_t h, double* out, const double* num, const double* den, int negate)
 { hipLaunchKernelGGL(divDeviceKernel<double>, dim3(1), dim3(1), 0, h->currentStream, out, num, den, negate); }
+
+/* ---- include/spgpu/ext/device_scalars_mv.h ---- */
+#define SPGPU_DEVICE_SCALARS_MV(L, T)                                                                                     \
+    void spgpu##L##mdotDevice(spgpuHandle_t h, T* result, int n, const T* a, const T* b, int count, int pitch)            \
+    { reduceVectorsToDevice<T, kDot>(h, result, n, a, b, count, pitch); }                                                 \
+    void spgpu##L##mnrm2Device(spgpuHandle_t h, T* result, int n, const T* x, int count, int pitch)                       \
+    { reduceVectorsToDevice<T, kNrm2>(h, result, n, x, (const T*)nullptr, count, pitch); }                                \
+    void spgpu##L##mdivDevice(spgpuHandle_t h, T* out, const T* num, const T* den, int negate, int count)                 \
+    { divFromDeviceMv<T>(h, out, num, den, negate, count); }                                                              \
+    void spgpu##L##maxpbyDevice(spgpuHandle_t h, T* z, int n, const T* beta, const T* y, const T* alpha, const T* x,      \
+                                int count, int pitch)                                                                     \
+    { axpbyFromDeviceMv<T>(h, z, n, beta != nullptr, beta, nullptr, y, alpha, nullptr, 0, x, count, pitch); }             \
+    void spgpu##L##maxpbyQuotDevice(spgpuHandle_t h, T* z, int n, const T* betaNum, const T* betaDen, const T* y,         \
+                                    const T* alphaNum, const T* alphaDen, int negateAlpha, const T* x, int count,         \
+                                    int pitch)                                                                            \
+    { axpbyFromDeviceMv<T>(h, z, n, 1, betaNum, betaDen, y, alphaNum, alphaDen, negateAlpha, x, count, pitch); }
+
+SPGPU_DEVICE_SCALARS_MV(S, float)
+SPGPU_DEVICE_SCALARS_MV(D, double)
 } // extern "C"

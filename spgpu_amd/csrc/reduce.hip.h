@@ -84,8 +84,8 @@ template <int MODE, typename Acc> static inline Acc finalOrder(const Acc* partia
 __device__ inline float squareRoot(float v) { return __builtin_sqrtf(v); }
 __device__ inline double squareRoot(double v) { return __builtin_sqrt(v); }
 
-template <typename Acc, int MODE, bool ROOT = false>
-__global__ __launch_bounds__(kWave) void reduceFinalKernel(Acc* result, const Acc* partials, int blocks)
+/* One wavefront combines the block partials of one vector in the order of finalOrder; every lane returns the total. */
+template <int MODE, typename Acc> __device__ inline Acc finalCombine(const Acc* partials, int blocks)
 {
     Acc mine[kFinalPerLane];
 #pragma unroll
@@ -100,12 +100,54 @@ __global__ __launch_bounds__(kWave) void reduceFinalKernel(Acc* result, const Ac
 #pragma unroll
     for (int m = 1; m < kWave; m <<= 1)
         sum = combine<MODE>(sum, laneXor(sum, m));
+    return sum;
+}
+
+template <typename Acc, int MODE, bool ROOT = false>
+__global__ __launch_bounds__(kWave) void reduceFinalKernel(Acc* result, const Acc* partials, int blocks)
+{
+    const Acc sum = finalCombine<MODE>(partials, blocks);
     if (threadIdx.x == 0) {
         if constexpr (ROOT)
             *result = squareRoot(sum); /* nrm2: sqrt of the unscaled sum of squares (dnrm2.cu:146) */
         else
             *result = sum;
     }
+}
+
+/* The same for the vectors of a multivector (spgpu/ext/device_scalars_mv.h): a grid of `vectors` wavefronts, wavefront j
+ * combines partials[j*blocks .. (j+1)*blocks) -- where the first stage's grid (blocks, vectors) left them -- into result[j]. */
+template <typename Acc, int MODE, bool ROOT = false>
+__global__ __launch_bounds__(kWave) void reduceFinalBatchKernel(Acc* result, const Acc* partials, int blocks)
+{
+    const Acc sum = finalCombine<MODE>(partials + (size_t)blockIdx.x * blocks, blocks);
+    if (threadIdx.x == 0) {
+        if constexpr (ROOT)
+            result[blockIdx.x] = squareRoot(sum);
+        else
+            result[blockIdx.x] = sum;
+    }
+}
+
+/* ---- the first stage's grid for a pass of a multivector (level1.hip reduceVectors and every call that must repeat its bits) ----
+ * The handle's scratch holds SPGPU_REDUCE_MAX_BLOCKS partials: a pass takes at most that many vectors, and its vectors share
+ * them, so each gets SPGPU_REDUCE_MAX_BLOCKS / vectors blocks at most.  16-byte accesses need the bases of the pass on 16 bytes
+ * and, beyond one vector, a pitch that keeps every vector there. */
+constexpr int kReduceMaxVectorsPerPass = SPGPU_REDUCE_MAX_BLOCKS;
+
+template <typename T> static inline bool reduceWide(const T* a, const T* b, int vectors, int pitch)
+{
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    return WIDE > 1 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) && (vectors == 1 || pitch % WIDE == 0);
+}
+
+template <typename T> static inline long long reduceBlocks(int n, bool wide, int vectors)
+{
+    constexpr int WIDE = 16 / (int)sizeof(T);
+    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
+    const long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
+    const long long cap = SPGPU_REDUCE_MAX_BLOCKS / vectors;
+    return blocks > cap ? cap : blocks;
 }
 
 } // namespace spgpu
