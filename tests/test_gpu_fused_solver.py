@@ -28,7 +28,9 @@ def _ragged_hell(letter, n, hack, base, seed):
 @pytest.mark.parametrize("with_beta", [False, True])
 def test_hellspmv_dot_device(gpu, letter, n, hack, base, offset, with_beta):
     """Ragged rows incl. empty ones, hack sizes that are / are not a multiple of the pack, rows not a multiple of the
-    pack, unaligned vectors (element mapping of the dot), more rows than one pass of the grid (2.1 M > 1024 x 2048)."""
+    pack, unaligned vectors (element mapping of the dot), more rows than one pass of the grid -- for fp64 only: 2 102 500 rows are
+    1 051 250 packs of two doubles, past the 1024 x 1024 packs one pass takes, but 525 625 packs of four floats, within it (the
+    second trip of fp32 and of the unpacked and narrow kernels: tests/test_gpu_fused_shapes.py).  beta == 0: y is full of NaN."""
     import torch
     import oracle_api as O
     from spgpu_amd import capi, formats, synth
@@ -43,7 +45,8 @@ def test_hellspmv_dot_device(gpu, letter, n, hack, base, offset, with_beta):
     w = synth.values_for(letter, 4, n + offset)[offset:]
     y = synth.values_for(letter, 5, n) if with_beta else None
     alpha, beta = (1.25, -0.5) if with_beta else (1.0, 0.0)
-    dx, dy = formats.to_device(x), formats.to_device(y)
+    dx = formats.to_device(x)
+    dy = formats.to_device(y) if with_beta else torch.full_like(dx, float("nan"))      # beta == 0: y must not be read
     dw = formats.to_device(synth.values_for(letter, 4, n + offset))[offset:]
     dz = torch.full((n + offset,), 7, dtype=dx.dtype, device="cuda:0")[offset:]
     out = torch.zeros(2, dtype=dx.dtype, device="cuda:0")
@@ -79,7 +82,8 @@ def test_hellspmv_dot_device_equals_default_spmv_on_a_stencil(gpu, letter):
     z1, z2 = torch.empty_like(dx), torch.empty_like(dx)
     out = torch.zeros(1, dtype=dx.dtype, device="cuda:0")
     mat.spmv(gpu, z1, None, 1.0, dx, 0.0)
-    capi.hellspmv_dot_device[letter](gpu, _p(out), None, _p(z2), None, capi.scalar(letter, 1.0), _p(mat.cM), _p(mat.rP), 32,
+    nan = torch.full_like(dx, float("nan"))                                            # beta == 0: y must not be read
+    capi.hellspmv_dot_device[letter](gpu, _p(out), None, _p(z2), _p(nan), capi.scalar(letter, 1.0), _p(mat.cM), _p(mat.rP), 32,
                                      _p(mat.hack_offsets), _p(mat.rS), n, _p(dx), capi.scalar(letter, 0.0), 0)
     torch.cuda.synchronize()
     if letter == "D":       # fp32's default kernel splits a row over 8 phases: same value within rounding only
