@@ -27,8 +27,6 @@
 #include "spgpu/device_scalars.h"
 #include "spgpu/ext/device_scalars_mv.h"
 
-#include <stdint.h>
-
 namespace spgpu {
 
 template <typename T> struct FusedSpmvArgs {
@@ -179,22 +177,11 @@ __global__ __launch_bounds__(kL1Threads) void hellSpmvDotKernel(FusedSpmvArgs<T>
         a.partials[blockIdx.x] = total;
 }
 
-/* Grid of the dot over n elements (level1.hip dotToDevice): the fused kernels must use the same one. */
-template <typename T> static long long dotBlocks(int n, bool wide)
-{
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    return blocks > SPGPU_REDUCE_MAX_BLOCKS ? SPGPU_REDUCE_MAX_BLOCKS : blocks;
-}
-
-static bool aligned(const void* p, size_t bytes) { return (uintptr_t)p % bytes == 0; }
-
+/* The grid of all three calls is that of the dot they replace (level1.hip reduceFirstStage), without its non-temporal kernel. */
 template <typename T>
 static void hellSpmvDot(spgpuHandle_t handle, T* result, const T* w, T* z, const T* y, T alpha, const T* cM, const int* rP,
                         int hackSize, const int* hackOffsets, const int* rS, int rows, const T* x, T beta, int baseIndex)
 {
-    constexpr int WIDE = 16 / (int)sizeof(T);
     hipStream_t s = handle->currentStream;
     FusedSpmvArgs<T> a;
     a.partials = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
@@ -213,26 +200,12 @@ static void hellSpmvDot(spgpuHandle_t handle, T* result, const T* w, T* z, const
     a.baseIndex = baseIndex;
     long long blocks = 0;
     if (rows > 0) {
-        const bool hasBeta = isNotZero(beta);
-        /* the dot's own choice (its operands are w and z) */
-        const bool wide = aligned(a.w, 16) && aligned(z, 16);
-        const bool packed = wide && hackSize % WIDE == 0 && aligned(cM, 16) && aligned(rP, 4 * WIDE) && aligned(rS, 4 * WIDE);
-        blocks = dotBlocks<T>(rows, wide);
-        const dim3 grid((unsigned)blocks), block(kL1Threads);
-#define SPGPU_FUSED_GO(VEC, PACKED)                                                                          \
-    do {                                                                                                     \
-        if (hasBeta)                                                                                         \
-            hipLaunchKernelGGL((hellSpmvDotKernel<T, VEC, PACKED, true>), grid, block, 0, s, a);             \
-        else                                                                                                 \
-            hipLaunchKernelGGL((hellSpmvDotKernel<T, VEC, PACKED, false>), grid, block, 0, s, a);            \
-    } while (0)
-        if (packed)
-            SPGPU_FUSED_GO(WIDE, true);
-        else if (wide)
-            SPGPU_FUSED_GO(WIDE, false);
-        else
-            SPGPU_FUSED_GO(1, false);
-#undef SPGPU_FUSED_GO
+        const L1Grid g = reduceGrid(sizeof(T), rows, 1, 0, a.w, z, false, SPGPU_REDUCE_MAX_BLOCKS); /* the dot's operands are w and z */
+        blocks = g.blocks;
+        withConstants([&](auto wide, auto packed, auto hasBeta) {
+            hipLaunchKernelGGL((hellSpmvDotKernel<T, wide ? wideOf(sizeof(T)) : 1, wide && packed, hasBeta>), dim3((unsigned)blocks),
+                               dim3(kL1Threads), 0, s, a);
+        }, g.wide, packedRows(sizeof(T), g.wide, hackSize, cM, rP, rS), isNotZero(beta));
     }
     hipLaunchKernelGGL((reduceFinalKernel<T, kDot>), dim3(1), dim3(kWave), 0, s, result, a.partials, (int)blocks);
     spgpuDebugCheck(handle, "hellspmvDotDevice");
@@ -317,19 +290,16 @@ template <typename T>
 static void axpbyPairDot(spgpuHandle_t handle, T* result, int n, T* z1, const T* y1, const T* x1, T* z2, const T* y2,
                          const T* x2, const T* alphaNum, const T* alphaDen)
 {
-    constexpr int WIDE = 16 / (int)sizeof(T);
     hipStream_t s = handle->currentStream;
     T* partials = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
     long long blocks = 0;
     if (n > 0) {
-        const bool wide = aligned(z2, 16); /* the dot's own choice: both of its operands are z2 */
-        blocks = dotBlocks<T>(n, wide);
-        if (wide)
-            hipLaunchKernelGGL((axpbyPairDotKernel<T, WIDE>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, partials, n, z1, y1,
-                               x1, z2, y2, x2, alphaNum, alphaDen);
-        else
-            hipLaunchKernelGGL((axpbyPairDotKernel<T, 1>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, partials, n, z1, y1, x1,
-                               z2, y2, x2, alphaNum, alphaDen);
+        const L1Grid g = reduceGrid(sizeof(T), n, 1, 0, z2, z2, false, SPGPU_REDUCE_MAX_BLOCKS); /* both operands of the dot are z2 */
+        blocks = g.blocks;
+        withConstants([&](auto wide) {
+            hipLaunchKernelGGL((axpbyPairDotKernel<T, wide ? wideOf(sizeof(T)) : 1>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s,
+                               partials, n, z1, y1, x1, z2, y2, x2, alphaNum, alphaDen);
+        }, g.wide);
     }
     hipLaunchKernelGGL((reduceFinalKernel<T, kDot>), dim3(1), dim3(kWave), 0, s, result, partials, (int)blocks);
     spgpuDebugCheck(handle, "axpbyPairDotDevice");
@@ -342,29 +312,24 @@ static void axpbyPairDotMv(spgpuHandle_t handle, T* result, int n, T* z1, const 
 {
     if (count <= 0)
         return;
-    constexpr int WIDE = 16 / (int)sizeof(T);
     hipStream_t s = handle->currentStream;
     T* partials = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
-    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
-        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
+    forEachPass(count, kReduceMaxVectorsPerPass, [&](int first, int vectors) {
         const size_t shift = (size_t)first * pitch;
         long long blocks = 0;
         if (n > 0) {
-            const bool wide = reduceWide<T>(z2 + shift, z2 + shift, vectors, pitch);
-            blocks = reduceBlocks<T>(n, wide, vectors);
-            const dim3 grid((unsigned)blocks, (unsigned)vectors);
-            const T* num = alphaNum ? alphaNum + first : nullptr;
-            const T* den = alphaDen ? alphaDen + first : nullptr;
-            if (wide)
-                hipLaunchKernelGGL((axpbyPairDotMvKernel<T, WIDE>), grid, dim3(kL1Threads), 0, s, partials, n, z1 + shift,
-                                   y1 + shift, x1 + shift, z2 + shift, y2 + shift, x2 + shift, num, den, (long long)pitch);
-            else
-                hipLaunchKernelGGL((axpbyPairDotMvKernel<T, 1>), grid, dim3(kL1Threads), 0, s, partials, n, z1 + shift,
-                                   y1 + shift, x1 + shift, z2 + shift, y2 + shift, x2 + shift, num, den, (long long)pitch);
+            const L1Grid g = reduceGrid(sizeof(T), n, vectors, pitch, z2 + shift, z2 + shift, false, SPGPU_REDUCE_MAX_BLOCKS);
+            blocks = g.blocks;
+            withConstants([&](auto wide) {
+                hipLaunchKernelGGL((axpbyPairDotMvKernel<T, wide ? wideOf(sizeof(T)) : 1>), dim3((unsigned)blocks, (unsigned)vectors),
+                                   dim3(kL1Threads), 0, s, partials, n, z1 + shift, y1 + shift, x1 + shift, z2 + shift, y2 + shift,
+                                   x2 + shift, alphaNum ? alphaNum + first : nullptr, alphaDen ? alphaDen + first : nullptr,
+                                   (long long)pitch);
+            }, g.wide);
         }
         hipLaunchKernelGGL((reduceFinalBatchKernel<T, kDot>), dim3((unsigned)vectors), dim3(kWave), 0, s, result + first,
                            partials, (int)blocks);
-    }
+    });
     spgpuDebugCheck(handle, "maxpbyPairDotDevice");
 }
 

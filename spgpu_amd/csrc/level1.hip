@@ -35,8 +35,6 @@
 
 namespace spgpu {
 
-constexpr int kL1MaxBlocks = 16384; /* measured: 2 048 -> 64.7 %, 16 384 -> 71 % of 8 TB/s for axpby (tile-stride loop beyond) */
-
 /* ---- axpby ---------------------------------------------------------------
  * Expression trees (reference): S/D  alpha*x + beta*y   (daxpby.cu:40-43)
  *                               C    fma(beta, y, alpha*x)  (caxpby.cu:44)
@@ -171,43 +169,11 @@ static void axpbyLaunch(spgpuHandle_t handle, ApiT* zApi, int n, ApiT betaApi, A
     __builtin_memcpy(&beta, &betaApi, sizeof(T));
     const bool hasBeta = isNotZero(beta);
 
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const bool wide = WIDE > 1 && ((uintptr_t)z % 16 == 0) && ((uintptr_t)x % 16 == 0) &&
-                      (!hasBeta || (uintptr_t)y % 16 == 0) && (count == 1 || pitch % WIDE == 0);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    const long long cap = kL1MaxBlocks / (count < kL1MaxBlocks ? count : kL1MaxBlocks);
-    if (blocks > (cap > 1 ? cap : 1))
-        blocks = cap > 1 ? cap : 1;
-    const dim3 grid((unsigned)blocks, (unsigned)count);
-    hipStream_t s = handle->currentStream;
-    /* Vectors larger than the 256 MiB Infinity Cache cannot be found there again by the next kernel: stream them
-     * with the non-temporal hint (measured, n = 1e8: 70-71 % -> 75.5-77 % of the HBM peak, profiles/r01d_level1_nt.txt).
-     * Smaller ones -- the vectors of a solver iteration -- stay cached. */
-    const long long streamed = (long long)n * (long long)sizeof(T) * count * (2 + (hasBeta ? 1 : 0));
-    const bool nt = streamed >= (256ll << 20); /* exact aliasing of z is fine: a lane reads its elements before it writes them */
-
-#define SPGPU_AXPBY_GO(VEC)                                                                               \
-    do {                                                                                                  \
-        if (hasBeta && nt)                                                                                \
-            hipLaunchKernelGGL((axpbyKernel<T, VEC, true, true>), grid, dim3(kL1Threads), 0, s, z, n, beta, y,   \
-                               alpha, x, (long long)pitch);                                               \
-        else if (hasBeta)                                                                                 \
-            hipLaunchKernelGGL((axpbyKernel<T, VEC, true>), grid, dim3(kL1Threads), 0, s, z, n, beta, y,   \
-                               alpha, x, (long long)pitch);                                               \
-        else if (nt)                                                                                      \
-            hipLaunchKernelGGL((axpbyKernel<T, VEC, false, true>), grid, dim3(kL1Threads), 0, s, z, n, beta, y,  \
-                               alpha, x, (long long)pitch);                                               \
-        else                                                                                              \
-            hipLaunchKernelGGL((axpbyKernel<T, VEC, false>), grid, dim3(kL1Threads), 0, s, z, n, beta, y,  \
-                               alpha, x, (long long)pitch);                                               \
-    } while (0)
-
-    if (wide)
-        SPGPU_AXPBY_GO(WIDE);
-    else
-        SPGPU_AXPBY_GO(1);
-#undef SPGPU_AXPBY_GO
+    const L1Grid g = axpbyGrid(sizeof(T), n, count, pitch, z, x, y, hasBeta); /* one launch; a narrow stream may go non-temporal too */
+    withConstants([&](auto wide, auto withBeta, auto nt) {
+        hipLaunchKernelGGL((axpbyKernel<T, wide ? wideOf(sizeof(T)) : 1, withBeta, nt>), dim3((unsigned)g.blocks, (unsigned)count),
+                           dim3(kL1Threads), 0, handle->currentStream, z, n, beta, y, alpha, x, (long long)pitch);
+    }, g.wide, hasBeta, g.nt);
     spgpuDebugCheck(handle, "axpby");
 }
 
@@ -313,27 +279,18 @@ __global__ __launch_bounds__(kL1Threads) void reduceKernel(typename AccOf<T, MOD
 
 /* First stage for one pass of `vectors` vectors (at most kReduceMaxVectorsPerPass) that start at a0 / b0: block partials go to
  * dev[j * blocks + block].  Returns blocks.  The one place that chooses kernel and grid for spgpu?mdot and for every call that
- * must repeat its bits (spgpu?mdotDevice, spgpu?mnrm2Device). */
+ * must repeat its bits (spgpu?dotDevice, spgpu?nrm2Device, spgpu?mdotDevice, spgpu?mnrm2Device).  mayStream: the non-temporal
+ * kernel is allowed (it never runs narrow). */
 template <typename T, int MODE>
 static long long reduceFirstStage(hipStream_t s, typename AccOf<T, MODE>::type* dev, int n, const T* a0, const T* b0, int vectors,
-                                  int pitch)
+                                  int pitch, bool mayStream)
 {
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const bool wide = reduceWide(a0, b0, vectors, pitch);
-    const long long blocks = reduceBlocks<T>(n, wide, vectors);
-    const dim3 grid((unsigned)blocks, (unsigned)vectors);
-
-    const long long streamed = (long long)n * (long long)sizeof(T) * vectors * (MODE == kDot ? 2 : 1);
-    if (wide && streamed >= (256ll << 20))
-        hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE, true>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                           (long long)pitch);
-    else if (wide)
-        hipLaunchKernelGGL((reduceKernel<T, WIDE, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                           (long long)pitch);
-    else
-        hipLaunchKernelGGL((reduceKernel<T, 1, MODE>), grid, dim3(kL1Threads), 0, s, dev, n, a0, b0,
-                           (long long)pitch);
-    return blocks;
+    const L1Grid g = reduceGrid(sizeof(T), n, vectors, pitch, a0, b0, mayStream, SPGPU_REDUCE_MAX_BLOCKS);
+    withConstants([&](auto wide, auto nt) {
+        hipLaunchKernelGGL((reduceKernel<T, wide ? wideOf(sizeof(T)) : 1, MODE, wide && nt>), dim3((unsigned)g.blocks, (unsigned)vectors),
+                           dim3(kL1Threads), 0, s, dev, n, a0, b0, (long long)pitch);
+    }, g.wide, g.nt);
+    return g.blocks;
 }
 
 /* Runs the two-stage reduction for `count` vectors and leaves one host value
@@ -353,12 +310,14 @@ static void reduceVectors(spgpuHandle_t handle, typename AccOf<T, MODE>::type* o
     Acc* dev = static_cast<Acc*>(priv->reduceScratch);
     Acc* host = static_cast<Acc*>(priv->reduceHost);
 
-    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
-        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
+    hipError_t status = hipSuccess;
+    forEachPass(count, kReduceMaxVectorsPerPass, [&](int first, int vectors) {
+        if (status != hipSuccess)
+            return; /* a pass before this one failed, and said so in every out[] from its own on */
         const T* a0 = a + (size_t)first * pitch;
         const T* b0 = MODE == kDot ? b + (size_t)first * pitch : nullptr;
-        const long long blocks = reduceFirstStage<T, MODE>(s, dev, n, a0, b0, vectors, pitch);
-        hipError_t status = hipMemcpyAsync(host, dev, sizeof(Acc) * (size_t)blocks * vectors, hipMemcpyDeviceToHost, s);
+        const long long blocks = reduceFirstStage<T, MODE>(s, dev, n, a0, b0, vectors, pitch, true);
+        status = hipMemcpyAsync(host, dev, sizeof(Acc) * (size_t)blocks * vectors, hipMemcpyDeviceToHost, s);
         if (status == hipSuccess)
             status = hipStreamSynchronize(s);
         if (status != hipSuccess) {
@@ -368,63 +327,25 @@ static void reduceVectors(spgpuHandle_t handle, typename AccOf<T, MODE>::type* o
             fprintf(stderr, "spgpu: reduction failed: %s\n", hipGetErrorString(status));
             return;
         }
-
-        for (int j = 0; j < vectors; ++j) {
+        for (int j = 0; j < vectors; ++j)
             out[first + j] = finalOrder<MODE>(host + (size_t)j * blocks, blocks);
-        }
-    }
-    spgpuDebugCheck(handle, "reduction");
+    });
+    if (status == hipSuccess)
+        spgpuDebugCheck(handle, "reduction");
 }
 
 
-/* dot with the result left in device memory: same first stage and same grid as reduceVectors for one vector;
- * no copy, no synchronisation (capturable in a graph). */
-template <typename T>
-static void dotToDevice(spgpuHandle_t handle, T* result, int n, const T* a, const T* b)
+/* dot / nrm2 with the result left in device memory: first stage and grid of spgpu?dot / spgpu?nrm2 on one vector -- but never
+ * their non-temporal kernel --, nrm2's square root taken by the final stage's lane; no copy, no synchronisation (capturable in a
+ * graph). */
+template <typename T, int MODE>
+static void reduceToDevice(spgpuHandle_t handle, T* result, int n, const T* a, const T* b, const char* what)
 {
     hipStream_t s = handle->currentStream;
     T* dev = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
-    long long blocks = 0;
-    if (n > 0) {
-        constexpr int WIDE = 16 / (int)sizeof(T);
-        const bool wide = WIDE > 1 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0);
-        const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-        blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-        if (blocks > SPGPU_REDUCE_MAX_BLOCKS)
-            blocks = SPGPU_REDUCE_MAX_BLOCKS;
-        const dim3 grid((unsigned)blocks, 1);
-        if (wide)
-            hipLaunchKernelGGL((reduceKernel<T, WIDE, kDot>), grid, dim3(kL1Threads), 0, s, dev, n, a, b, 0ll);
-        else
-            hipLaunchKernelGGL((reduceKernel<T, 1, kDot>), grid, dim3(kL1Threads), 0, s, dev, n, a, b, 0ll);
-    }
-    hipLaunchKernelGGL((reduceFinalKernel<T, kDot>), dim3(1), dim3(kWave), 0, s, result, dev, (int)blocks);
-    spgpuDebugCheck(handle, "dotDevice");
-}
-
-/* nrm2 with the result left in device memory: first stage and grid of spgpu?nrm2, the square root taken by the final
- * stage's lane. */
-template <typename T>
-static void nrm2ToDevice(spgpuHandle_t handle, T* result, int n, const T* a)
-{
-    hipStream_t s = handle->currentStream;
-    T* dev = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
-    long long blocks = 0;
-    if (n > 0) {
-        constexpr int WIDE = 16 / (int)sizeof(T);
-        const bool wide = WIDE > 1 && ((uintptr_t)a % 16 == 0);
-        const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-        blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-        if (blocks > SPGPU_REDUCE_MAX_BLOCKS)
-            blocks = SPGPU_REDUCE_MAX_BLOCKS;
-        const dim3 grid((unsigned)blocks, 1);
-        if (wide)
-            hipLaunchKernelGGL((reduceKernel<T, WIDE, kNrm2>), grid, dim3(kL1Threads), 0, s, dev, n, a, (const T*)nullptr, 0ll);
-        else
-            hipLaunchKernelGGL((reduceKernel<T, 1, kNrm2>), grid, dim3(kL1Threads), 0, s, dev, n, a, (const T*)nullptr, 0ll);
-    }
-    hipLaunchKernelGGL((reduceFinalKernel<T, kNrm2, true>), dim3(1), dim3(kWave), 0, s, result, dev, (int)blocks);
-    spgpuDebugCheck(handle, "nrm2Device");
+    const long long blocks = n > 0 ? reduceFirstStage<T, MODE>(s, dev, n, a, b, 1, 0, false) : 0;
+    hipLaunchKernelGGL((reduceFinalKernel<T, MODE, MODE == kNrm2>), dim3(1), dim3(kWave), 0, s, result, dev, (int)blocks);
+    spgpuDebugCheck(handle, what);
 }
 
 /* dot / nrm2 of a pitch multivector with one result per vector left in device memory (spgpu/ext/device_scalars_mv.h):
@@ -437,15 +358,14 @@ static void reduceVectorsToDevice(spgpuHandle_t handle, T* result, int n, const 
         return;
     hipStream_t s = handle->currentStream;
     T* dev = static_cast<T*>(spgpuPrivate(handle)->reduceScratch);
-    for (int first = 0; first < count; first += kReduceMaxVectorsPerPass) {
-        const int vectors = count - first < kReduceMaxVectorsPerPass ? count - first : kReduceMaxVectorsPerPass;
+    forEachPass(count, kReduceMaxVectorsPerPass, [&](int first, int vectors) {
         long long blocks = 0; /* n <= 0: no first stage, every result of the pass is +0 */
         if (n > 0)
             blocks = reduceFirstStage<T, MODE>(s, dev, n, a + (size_t)first * pitch,
-                                               MODE == kDot ? b + (size_t)first * pitch : nullptr, vectors, pitch);
+                                               MODE == kDot ? b + (size_t)first * pitch : nullptr, vectors, pitch, true);
         hipLaunchKernelGGL((reduceFinalBatchKernel<T, MODE, MODE == kNrm2>), dim3((unsigned)vectors), dim3(kWave), 0, s,
                            result + first, dev, (int)blocks);
-    }
+    });
     spgpuDebugCheck(handle, "multivector reduction to device");
 }
 
@@ -455,20 +375,12 @@ static void axpbyFromDevice(spgpuHandle_t handle, T* z, int n, int hasBeta, cons
 {
     if (n <= 0)
         return;
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    /* y may be ignored at run time (beta == 0); its alignment is required only when it is given */
-    const bool wide = ((uintptr_t)z % 16 == 0) && ((uintptr_t)x % 16 == 0) && (!hasBeta || !y || (uintptr_t)y % 16 == 0);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    if (blocks > kL1MaxBlocks)
-        blocks = kL1MaxBlocks;
-    hipStream_t s = handle->currentStream;
-    if (wide)
-        hipLaunchKernelGGL((axpbyDeviceKernel<T, WIDE>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, z, n, hasBeta, betaNum,
-                           betaDen, y, alphaNum, alphaDen, negateAlpha, x);
-    else
-        hipLaunchKernelGGL((axpbyDeviceKernel<T, 1>), dim3((unsigned)blocks), dim3(kL1Threads), 0, s, z, n, hasBeta, betaNum,
-                           betaDen, y, alphaNum, alphaDen, negateAlpha, x);
+    /* y may be ignored at run time (beta == 0); its alignment is required only when it is given (NULL is on every boundary) */
+    const L1Grid g = axpbyDeviceGrid(sizeof(T), n, 1, 1, 0, z, x, y, hasBeta != 0);
+    withConstants([&](auto wide) {
+        hipLaunchKernelGGL((axpbyDeviceKernel<T, wide ? wideOf(sizeof(T)) : 1>), dim3((unsigned)g.blocks), dim3(kL1Threads), 0,
+                           handle->currentStream, z, n, hasBeta, betaNum, betaDen, y, alphaNum, alphaDen, negateAlpha, x);
+    }, g.wide);
     spgpuDebugCheck(handle, "axpbyDevice");
 }
 
@@ -480,28 +392,17 @@ static void axpbyFromDeviceMv(spgpuHandle_t handle, T* z, int n, int hasBeta, co
 {
     if (n <= 0 || count <= 0)
         return;
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    /* which vectors read y is known on the device only; its alignment is required whenever it is given */
-    const bool wide = ((uintptr_t)z % 16 == 0) && ((uintptr_t)x % 16 == 0) && (!hasBeta || !y || (uintptr_t)y % 16 == 0) &&
-                      (count == 1 || pitch % WIDE == 0);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    hipStream_t s = handle->currentStream;
-    for (int first = 0; first < count; first += kL1MaxBlocks) {
-        const int vectors = count - first < kL1MaxBlocks ? count - first : kL1MaxBlocks;
-        long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-        if (blocks > kL1MaxBlocks / vectors)
-            blocks = kL1MaxBlocks / vectors;
-        const dim3 grid((unsigned)blocks, (unsigned)vectors);
+    /* passes of kL1MaxBlocks vectors; `wide` is one choice for the whole call (its bases, its count) */
+    forEachPass(count, kL1MaxBlocks, [&](int first, int vectors) {
+        const L1Grid g = axpbyDeviceGrid(sizeof(T), n, count, vectors, pitch, z, x, y, hasBeta != 0);
         const size_t shift = (size_t)first * pitch;
-        if (wide)
-            hipLaunchKernelGGL((axpbyDeviceMvKernel<T, WIDE>), grid, dim3(kL1Threads), 0, s, z + shift, n, hasBeta,
-                               scalarAt(betaNum, first), scalarAt(betaDen, first), y ? y + shift : y, scalarAt(alphaNum, first),
-                               scalarAt(alphaDen, first), negateAlpha, x + shift, (long long)pitch);
-        else
-            hipLaunchKernelGGL((axpbyDeviceMvKernel<T, 1>), grid, dim3(kL1Threads), 0, s, z + shift, n, hasBeta,
-                               scalarAt(betaNum, first), scalarAt(betaDen, first), y ? y + shift : y, scalarAt(alphaNum, first),
-                               scalarAt(alphaDen, first), negateAlpha, x + shift, (long long)pitch);
-    }
+        withConstants([&](auto wide) {
+            hipLaunchKernelGGL((axpbyDeviceMvKernel<T, wide ? wideOf(sizeof(T)) : 1>), dim3((unsigned)g.blocks, (unsigned)vectors),
+                               dim3(kL1Threads), 0, handle->currentStream, z + shift, n, hasBeta, scalarAt(betaNum, first),
+                               scalarAt(betaDen, first), y ? y + shift : y, scalarAt(alphaNum, first), scalarAt(alphaDen, first),
+                               negateAlpha, x + shift, (long long)pitch);
+        }, g.wide);
+    });
     spgpuDebugCheck(handle, "maxpbyDevice");
 }
 
@@ -510,7 +411,7 @@ static void divFromDeviceMv(spgpuHandle_t handle, T* out, const T* num, const T*
 {
     if (count <= 0)
         return;
-    hipLaunchKernelGGL(divDeviceMvKernel<T>, dim3((unsigned)((count + kL1Threads - 1) / kL1Threads)), dim3(kL1Threads), 0,
+    hipLaunchKernelGGL(divDeviceMvKernel<T>, dim3((unsigned)ceilDiv(count, kL1Threads)), dim3(kL1Threads), 0,
                        handle->currentStream, out, num, den, negate, count);
     spgpuDebugCheck(handle, "mdivDevice");
 }
@@ -607,28 +508,13 @@ static void mapLaunch(spgpuHandle_t handle, ApiT* outApi, int n, ApiT alphaApi, 
     __builtin_memcpy(&one, &unit, sizeof(R)); /* (1) or (1, 0) */
     const int alphaIsOne = __builtin_memcmp(&alpha, &one, sizeof(T)) == 0;
 
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const bool wide = WIDE > 1 && ((uintptr_t)out % 16 == 0) && ((uintptr_t)x % 16 == 0) &&
-                      (OP < kAxy || (uintptr_t)y % 16 == 0) && (OP != kAxypbz || (uintptr_t)z % 16 == 0) &&
-                      (count == 1 || pitch % WIDE == 0);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    const long long cap = kL1MaxBlocks / (count < kL1MaxBlocks ? count : kL1MaxBlocks);
-    if (blocks > (cap > 1 ? cap : 1))
-        blocks = cap > 1 ? cap : 1;
-    const dim3 grid((unsigned)blocks, (unsigned)count);
-    hipStream_t s = handle->currentStream;
-    /* same rule as axpby: streams beyond the Infinity Cache go non-temporal */
-    const long long streamed = (long long)n * (long long)sizeof(T) * count * (OP == kAxypbz ? 4 : OP == kAxy ? 3 : 2);
-    if (wide && streamed >= (256ll << 20))
-        hipLaunchKernelGGL((mapKernel<T, WIDE, OP, true>), grid, dim3(kL1Threads), 0, s, out, n, alpha, beta, x, y, z,
-                           (long long)pitch, alphaIsOne);
-    else if (wide)
-        hipLaunchKernelGGL((mapKernel<T, WIDE, OP>), grid, dim3(kL1Threads), 0, s, out, n, alpha, beta, x, y, z,
-                           (long long)pitch, alphaIsOne);
-    else
-        hipLaunchKernelGGL((mapKernel<T, 1, OP>), grid, dim3(kL1Threads), 0, s, out, n, alpha, beta, x, y, z,
-                           (long long)pitch, alphaIsOne);
+    /* one launch; only the operands the operation reads count, each a stream; only 16-byte streams go non-temporal */
+    const L1Grid g = mapGrid(sizeof(T), n, count, pitch, {out, x, OP >= kAxy ? y : nullptr, OP == kAxypbz ? z : nullptr},
+                             OP == kAxypbz ? 4 : OP == kAxy ? 3 : 2);
+    withConstants([&](auto wide, auto nt) {
+        hipLaunchKernelGGL((mapKernel<T, wide ? wideOf(sizeof(T)) : 1, OP, wide && nt>), dim3((unsigned)g.blocks, (unsigned)count),
+                           dim3(kL1Threads), 0, handle->currentStream, out, n, alpha, beta, x, y, z, (long long)pitch, alphaIsOne);
+    }, g.wide, g.nt);
     spgpuDebugCheck(handle, "level-1 map");
 }
 
@@ -684,7 +570,7 @@ template <typename T> __global__ __launch_bounds__(kL1Threads) void fillKernel(T
 
 static unsigned sparseGrid(long long count)
 {
-    long long blocks = (count + kL1Threads - 1) / kL1Threads;
+    const long long blocks = ceilDiv(count, kL1Threads);
     return (unsigned)(blocks > 4 * kL1MaxBlocks ? 4 * kL1MaxBlocks : (blocks < 1 ? 1 : blocks));
 }
 
@@ -842,24 +728,21 @@ void spgpuIsetscal(spgpuHandle_t h, int first, int last, int baseIndex, int val,
 
 
 /* ---- include/spgpu/device_scalars.h ---- */
-void spgpuSdotDevice(spgpuHandle_t h, float* result, int n, const float* a, const float* b) { dotToDevice<float>(h, result, n, a, b); }
-void spgpuDdotDevice(spgpuHandle_t h, double* result, int n, const double* a, const double* b) { dotToDevice<double>(h, result, n, a, b); }
-void spgpuSnrm2Device(spgpuHandle_t h, float* result, int n, const float* a) { nrm2ToDevice<float>(h, result, n, a); }
-void spgpuDnrm2Device(spgpuHandle_t h, double* result, int n, const double* a) { nrm2ToDevice<double>(h, result, n, a); }
-void spgpuSaxpbyDevice(spgpuHandle_t h, float* z, int n, const float* beta, const float* y, const float* alpha, const float* x)
-{ axpbyFromDevice<float>(h, z, n, beta != nullptr, beta, nullptr, y, alpha, nullptr, 0, x); }
-void spgpuSaxpbyQuotDevice(spgpuHandle_t h, float* z, int n, const float* betaNum, const float* betaDen, const float* y,
-                           const float* alphaNum, const float* alphaDen, int negateAlpha, const float* x)
-{ axpbyFromDevice<float>(h, z, n, 1, betaNum, betaDen, y, alphaNum, alphaDen, negateAlpha, x); }
-void spgpuDaxpbyDevice(spgpuHandle_t h, double* z, int n, const double* beta, const double* y, const double* alpha, const double* x)
-{ axpbyFromDevice<double>(h, z, n, beta != nullptr, beta, nullptr, y, alpha, nullptr, 0, x); }
-void spgpuDaxpbyQuotDevice(spgpuHandle_t h, double* z, int n, const double* betaNum, const double* betaDen, const double* y,
-                           const double* alphaNum, const double* alphaDen, int negateAlpha, const double* x)
-{ axpbyFromDevice<double>(h, z, n, 1, betaNum, betaDen, y, alphaNum, alphaDen, negateAlpha, x); }
-void spgpuSdivDevice(spgpuHandle_t h, float* out, const float* num, const float* den, int negate)
-{ hipLaunchKernelGGL(divDeviceKernel<float>, dim3(1), dim3(1), 0, h->currentStream, out, num, den, negate); }
-void spgpuDdivDevice(spgpuHandle_t h, double* out, const double* num, const double* den, int negate)
-{ hipLaunchKernelGGL(divDeviceKernel<double>, dim3(1), dim3(1), 0, h->currentStream, out, num, den, negate); }
+#define SPGPU_DEVICE_SCALARS(L, T)                                                                                        \
+    void spgpu##L##dotDevice(spgpuHandle_t h, T* result, int n, const T* a, const T* b)                                   \
+    { reduceToDevice<T, kDot>(h, result, n, a, b, "dotDevice"); }                                                         \
+    void spgpu##L##nrm2Device(spgpuHandle_t h, T* result, int n, const T* a)                                              \
+    { reduceToDevice<T, kNrm2>(h, result, n, a, (const T*)nullptr, "nrm2Device"); }                                       \
+    void spgpu##L##axpbyDevice(spgpuHandle_t h, T* z, int n, const T* beta, const T* y, const T* alpha, const T* x)       \
+    { axpbyFromDevice<T>(h, z, n, beta != nullptr, beta, nullptr, y, alpha, nullptr, 0, x); }                             \
+    void spgpu##L##axpbyQuotDevice(spgpuHandle_t h, T* z, int n, const T* betaNum, const T* betaDen, const T* y,          \
+                                   const T* alphaNum, const T* alphaDen, int negateAlpha, const T* x)                     \
+    { axpbyFromDevice<T>(h, z, n, 1, betaNum, betaDen, y, alphaNum, alphaDen, negateAlpha, x); }                          \
+    void spgpu##L##divDevice(spgpuHandle_t h, T* out, const T* num, const T* den, int negate)                             \
+    { hipLaunchKernelGGL(divDeviceKernel<T>, dim3(1), dim3(1), 0, h->currentStream, out, num, den, negate); }
+
+SPGPU_DEVICE_SCALARS(S, float)
+SPGPU_DEVICE_SCALARS(D, double)
 
 /* ---- include/spgpu/ext/device_scalars_mv.h ---- */
 #define SPGPU_DEVICE_SCALARS_MV(L, T)                                                                                     \

@@ -5,16 +5,13 @@
  * wavefront, the 4 wavefront sums added in wavefront order, block partials combined in the fixed order of finalOrder.
  * Reference shape: kernels/ddot.cu:35-150 (per-block partials, host adds them).
  */
+#include "level1_grid.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
 namespace spgpu {
 
-constexpr int kL1Threads = 256;
-constexpr int kL1Unroll = 4; /* independent 16-byte accesses in flight per lane */
 enum ReduceMode { kDot = 0, kNrm2 = 1, kAsum = 2, kAmax = 3 };
-
-
 
 /* A coefficient given as num/den in device memory (NULL = 1). */
 template <typename T> __device__ inline T quotientAt(const T* num, const T* den)
@@ -129,25 +126,8 @@ __global__ __launch_bounds__(kWave) void reduceFinalBatchKernel(Acc* result, con
     }
 }
 
-/* ---- the first stage's grid for a pass of a multivector (level1.hip reduceVectors and every call that must repeat its bits) ----
- * The handle's scratch holds SPGPU_REDUCE_MAX_BLOCKS partials: a pass takes at most that many vectors, and its vectors share
- * them, so each gets SPGPU_REDUCE_MAX_BLOCKS / vectors blocks at most.  16-byte accesses need the bases of the pass on 16 bytes
- * and, beyond one vector, a pitch that keeps every vector there. */
+/* The handle's scratch holds SPGPU_REDUCE_MAX_BLOCKS partials: a pass of a multivector takes at most that many vectors, and they
+ * share them (level1_grid.h reduceGrid with cap = SPGPU_REDUCE_MAX_BLOCKS). */
 constexpr int kReduceMaxVectorsPerPass = SPGPU_REDUCE_MAX_BLOCKS;
-
-template <typename T> static inline bool reduceWide(const T* a, const T* b, int vectors, int pitch)
-{
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    return WIDE > 1 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) && (vectors == 1 || pitch % WIDE == 0);
-}
-
-template <typename T> static inline long long reduceBlocks(int n, bool wide, int vectors)
-{
-    constexpr int WIDE = 16 / (int)sizeof(T);
-    const long long work = wide ? ((long long)n + WIDE - 1) / WIDE : n;
-    const long long blocks = (work + kL1Threads * kL1Unroll - 1) / (kL1Threads * kL1Unroll);
-    const long long cap = SPGPU_REDUCE_MAX_BLOCKS / vectors;
-    return blocks > cap ? cap : blocks;
-}
 
 } // namespace spgpu

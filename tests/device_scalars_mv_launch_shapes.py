@@ -1,15 +1,15 @@
-"""The constants of the host dispatch behind include/spgpu/ext/device_scalars_mv.h (spgpu_amd/csrc/level1.hip, reduce.hip.h,
-fused_solver.hip), that dispatch restated as a function of what a caller passes, and the case table tests/test_gpu_device_scalars_mv.py
+"""The constants of the host dispatch behind include/spgpu/ext/device_scalars_mv.h (spgpu_amd/csrc/level1_grid.h, called from level1.hip
+and fused_solver.hip), that dispatch restated as a function of what a caller passes, and the case table tests/test_gpu_device_scalars_mv.py
 runs -- stated once for that module (which runs the cases on the GPU) and for tests/test_device_scalars_mv_launch_shapes.py (which
 checks on the CPU that the table reaches every branch, and that each case reaches the branches it is there for).  No torch, no library:
 importable everywhere."""
 
 # ---- the constants of the dispatch: a change there is a test to revisit here ------------------------------------------------------
-THREADS = 256                 # reduce.hip.h     kL1Threads
-UNROLL = 4                    # reduce.hip.h     kL1Unroll: 16-byte accesses in flight per lane
+THREADS = 256                 # level1_grid.h    kL1Threads
+UNROLL = 4                    # level1_grid.h    kL1Unroll: 16-byte accesses in flight per lane
 TILE = THREADS * UNROLL       # packs (wide) or elements (narrow) one workgroup takes per trip
 REDUCE_MAX_BLOCKS = 1024      # spgpu_internal.h SPGPU_REDUCE_MAX_BLOCKS: partials the scratch holds = vectors of a pass = blocks they share
-L1_MAX_BLOCKS = 16384         # level1.hip       kL1MaxBlocks: the same two roles for the updates
+L1_MAX_BLOCKS = 16384         # level1_grid.h    kL1MaxBlocks: the same two roles for the updates
 LETTERS = "SD"
 SIZEOF = {"S": 4, "D": 8}
 WIDE = {L: 16 // SIZEOF[L] for L in LETTERS}      # elements of a 16-byte access: S 4, D 2
@@ -20,7 +20,7 @@ def _ceil(a, b):
 
 
 def reduce_passes(letter, n, count, pitch, off_a=0, off_b=0):
-    """reduceVectorsToDevice / reduceVectors (level1.hip) and reduceWide / reduceBlocks (reduce.hip.h) restated: the passes of
+    """reduceVectorsToDevice / reduceVectors (level1.hip) over forEachPass / reduceGrid (level1_grid.h) restated: the passes of
     spgpu?mdotDevice, each dict(vectors, wide, blocks, cap_binds).  off_a, off_b: bytes by which the bases lie past a 16-byte
     boundary (nrm2: off_b = 0; the pair-dot: both those of z2).  count <= 0: no pass.  n <= 0: passes without a first stage
     (blocks 0)."""
@@ -50,7 +50,7 @@ def repeats_single_vector_call(letter, n, count, pitch, *offs):
 
 
 def update_launch(letter, n, count, pitch, off_z=0, off_x=0, off_y=None, beta_given=True):
-    """axpbyFromDeviceMv (level1.hip) restated: None where nothing is launched, else dict(wide, blocks) of the (only, for
+    """axpbyFromDeviceMv (level1.hip) over axpbyDeviceGrid (level1_grid.h) restated: None where nothing is launched, else dict(wide, blocks) of the (only, for
     count <= 16384) pass.  off_y None: y == NULL; beta_given False: spgpu?maxpbyDevice with beta == NULL (y is never read)."""
     if n <= 0 or count <= 0:
         return None

@@ -10,14 +10,14 @@ import functools
 import numpy as np
 
 # ---- the constants of the dispatch: a change there is a test to revisit here ------------------------------------------------------
-kL1Threads = 256                    # reduce.hip.h     kL1Threads
-kL1Unroll = 4                       # reduce.hip.h     kL1Unroll: 16-byte accesses in flight per lane
+kL1Threads = 256                    # level1_grid.h    kL1Threads
+kL1Unroll = 4                       # level1_grid.h    kL1Unroll: 16-byte accesses in flight per lane
 SPGPU_REDUCE_MAX_BLOCKS = 1024      # spgpu_internal.h SPGPU_REDUCE_MAX_BLOCKS: block partials the handle's scratch holds
 kWave = 64                          # numeric.hip.h    kWave: lanes that share one __ballot
 TILE = kL1Threads * kL1Unroll       # packs one workgroup takes per trip of the tile-stride loop
 LETTERS = "SD"
 SIZEOF = {"S": 4, "D": 8}
-WIDE = {L: 16 // SIZEOF[L] for L in LETTERS}      # fused_solver.hip: WIDE = 16 / sizeof(T): S 4, D 2
+WIDE = {L: 16 // SIZEOF[L] for L in LETTERS}      # level1_grid.h: wideOf(sizeof(T)): S 4, D 2
 PATHS = ("narrow", "wide", "packed")
 
 
@@ -26,7 +26,7 @@ def _ceil(a, b):
 
 
 def _grid(letter, n, wide):
-    """dotBlocks (fused_solver.hip) and the loop of the kernels restated for n elements."""
+    """blocks() of level1_grid.h with the reduction's cap and the loop of the kernels restated for n elements."""
     vec = WIDE[letter] if wide else 1
     need = _ceil(_ceil(n, WIDE[letter]) if wide else n, TILE)
     blocks = min(need, SPGPU_REDUCE_MAX_BLOCKS)
@@ -38,7 +38,7 @@ def _grid(letter, n, wide):
 
 
 def spmv_dot_launch(letter, rows, hack, off_w=0, off_z=0, off_cM=0, off_rP=0, off_rS=0, beta=0):
-    """hellSpmvDot restated.  off_*: bytes by which an array lies past a 16-byte boundary (w: the array the dot reads, x when the
+    """hellSpmvDot over reduceGrid / packedRows (level1_grid.h) restated.  off_*: bytes by which an array lies past a 16-byte boundary (w: the array the dot reads, x when the
     caller passes w == NULL).  None where no first stage is launched (rows <= 0), else dict(path, has_beta, blocks, cap_binds, trips
     (of workgroup 0), last_trip_partial, tail (rows the tail code takes), vec, packs)."""
     if rows <= 0:

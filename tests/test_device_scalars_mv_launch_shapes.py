@@ -17,11 +17,11 @@ def _source(name):
 
 
 def test_the_constants_are_those_of_the_sources():
-    reduce_h, internal, level1 = _source("reduce.hip.h"), _source("spgpu_internal.h"), _source("level1.hip")
-    assert f"constexpr int kL1Threads = {M.THREADS};" in reduce_h and f"constexpr int kL1Unroll = {M.UNROLL};" in reduce_h
+    reduce_h, internal, grid = _source("reduce.hip.h"), _source("spgpu_internal.h"), _source("level1_grid.h")
+    assert f"constexpr int kL1Threads = {M.THREADS};" in grid and f"constexpr int kL1Unroll = {M.UNROLL};" in grid
     assert re.search(rf"#define SPGPU_REDUCE_MAX_BLOCKS {M.REDUCE_MAX_BLOCKS}\b", internal)
     assert "constexpr int kReduceMaxVectorsPerPass = SPGPU_REDUCE_MAX_BLOCKS;" in reduce_h
-    assert f"constexpr int kL1MaxBlocks = {M.L1_MAX_BLOCKS};" in level1
+    assert f"constexpr int kL1MaxBlocks = {M.L1_MAX_BLOCKS};" in grid
 
 
 @pytest.mark.parametrize("letter", M.LETTERS)

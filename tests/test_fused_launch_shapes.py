@@ -1,5 +1,5 @@
 """CPU: the case table of tests/test_gpu_fused_shapes.py reaches every branch of the host dispatch of the fused CG steps
-(spgpu_amd/csrc/fused_solver.hip) and of the strip choice inside rowSums, each case reaches the branches it is there for, the
+(spgpu_amd/csrc/fused_solver.hip over level1_grid.h) and of the strip choice inside rowSums, each case reaches the branches it is there for, the
 restated dispatch (tests/fused_launch_shapes.py) still states the constants the sources state, and the integer inputs of every
 case that claims exact sums satisfy the condition under which they are exact."""
 import os
@@ -20,16 +20,14 @@ def _source(name):
 
 
 def test_the_constants_are_those_of_the_sources():
-    reduce_h, internal, numeric, fused = (_source(n) for n in ("reduce.hip.h", "spgpu_internal.h", "numeric.hip.h", "fused_solver.hip"))
-    assert f"constexpr int kL1Threads = {M.kL1Threads};" in reduce_h and f"constexpr int kL1Unroll = {M.kL1Unroll};" in reduce_h
+    grid, internal, numeric = (_source(n) for n in ("level1_grid.h", "spgpu_internal.h", "numeric.hip.h"))
+    assert f"constexpr int kL1Threads = {M.kL1Threads};" in grid and f"constexpr int kL1Unroll = {M.kL1Unroll};" in grid
     assert re.search(rf"#define SPGPU_REDUCE_MAX_BLOCKS {M.SPGPU_REDUCE_MAX_BLOCKS}\b", internal)
     assert re.search(rf"constexpr int kWave = {M.kWave};", numeric)
-    assert fused.count("constexpr int WIDE = 16 / (int)sizeof(T);") >= 3
+    assert "constexpr int wideOf(size_t elemBytes) { return (int)(16 / elemBytes); }" in grid
     assert M.WIDE == {"S": 4, "D": 2} and M.TILE == 1024
-    # the conditions the restated dispatch repeats
-    assert "const bool wide = aligned(a.w, 16) && aligned(z, 16);" in fused
-    assert "hackSize % WIDE == 0 && aligned(cM, 16) && aligned(rP, 4 * WIDE) && aligned(rS, 4 * WIDE)" in fused
-    assert "const bool wide = aligned(z2, 16);" in fused
+    # the conditions the restated dispatch repeats (`wide` of w and z resp. of z2, `packed`) are those of level1_grid.h's reduceGrid and
+    # packedRows, which tests/test_level1_grid.py runs on every case of this table and compares with spmv_dot_launch / pair_dot_launch
 
 
 @pytest.mark.parametrize("letter", M.LETTERS)
