@@ -41,6 +41,7 @@
  *
  * Only S and D are offered, as for the SpMM and the single-vector device-scalar calls.  Measurements: tools/bench_mv_level1.py,
  * DESIGN.md section 3.9.
+ * The pair-dot with the Jacobi step of preconditioned CG inside (spgpu?maxpbyPairAxyDotDevice): spgpu/ext/precond.h.
  */
 #include "../core.h"
 

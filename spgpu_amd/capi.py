@@ -296,6 +296,21 @@ for _L in "SD":
     maxpby_pair_dot_device[_L] = _decl(f"spgpu{_L}maxpbyPairDotDevice", None,
                                        [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
 
+# ---- ext/precond.h: the diagonal of a matrix the library holds (the matrix arguments lead as in the matching spmv), and the Jacobi
+# step of PCG fused into the device-scalar calls; the m-forms take the single-vector argument lists, then count and pitch ----------
+hell_diag, ell_diag, hdia_diag = {}, {}, {}
+axy_dot_device, axpby_pair_axy_dot_device, maxy_dot_device, maxpby_pair_axy_dot_device = {}, {}, {}, {}
+for _L in "SD":
+    hell_diag[_L] = _decl(f"spgpu{_L}hellDiag", None, [Handle, ptr, ptr, ptr, i32, ptr, ptr, i32, i32, i32])
+    ell_diag[_L] = _decl(f"spgpu{_L}ellDiag", None, [Handle, ptr, ptr, ptr, i32, i32, ptr, i32, i32, i32, i32])
+    hdia_diag[_L] = _decl(f"spgpu{_L}hdiaDiag", None, [Handle, ptr, ptr, ptr, i32, ptr, i32, i32, i32])
+    axy_dot_device[_L] = _decl(f"spgpu{_L}axyDotDevice", None, [Handle, ptr, i32, ptr, ptr, ptr])
+    axpby_pair_axy_dot_device[_L] = _decl(f"spgpu{_L}axpbyPairAxyDotDevice", None,
+                                          [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr])
+    maxy_dot_device[_L] = _decl(f"spgpu{_L}maxyDotDevice", None, [Handle, ptr, i32, ptr, ptr, ptr, i32, i32])
+    maxpby_pair_axy_dot_device[_L] = _decl(f"spgpu{_L}maxpbyPairAxyDotDevice", None,
+                                           [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
+
 # ---- tuning.h: per-handle kernel-form hint ---------------------------------------------------------------------
 FORM_AUTO, FORM_GATHER, FORM_STRIPS, FORM_XTILE, FORM_SWEEP = range(5)
 spgpuSetSpmvForm = _decl("spgpuSetSpmvForm", None, [Handle, i32])

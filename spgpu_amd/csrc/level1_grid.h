@@ -16,6 +16,13 @@
  *   dotDevice, nrm2Device, axpbyPairDot, hellspmvDot (reduceGrid, one vector)
  *                                     one launch              cap                            never (spgpu?dot does: see DESIGN.md 3.9)
  *   maxpbyPairDot (reduceGrid)        passes of `cap` vectors cap / vectors of the pass      never (no such kernel)
+ *   axyDot, axpbyPairAxyDot (reduceGrid, one vector: on r and z, resp. on z2 as axpbyPairDot; d and w never count)
+ *                                     one launch              cap                            never (no such kernel)
+ *   maxyDot (reduceGrid)              passes of `cap` vectors cap / vectors of the pass      never (no such kernel)
+ *   maxpbyPairAxyDot (reduceGrid)     passes of `cap` vectors cap / vectors of the pass      never (no such kernel)
+ *                                     two sets of partials, [2][vectors][blocks], in a scratch of 2 * cap: a pass of more than
+ *                                     cap / 2 vectors (one workgroup each) runs as two launches of at most cap / 2 vectors on
+ *                                     the pass' grid and `wide`, so result[] keeps the bits of mdotDevice for every count
  *   axpbyDevice, maxpbyDevice (axpbyDeviceGrid)
  *                                     passes of kL1MaxBlocks  kL1MaxBlocks / vectors         never (no such kernel)
  * cap = SPGPU_REDUCE_MAX_BLOCKS (spgpu_internal.h), the partials the handle's scratch holds.  A reduction decides `wide` anew for every
