@@ -57,13 +57,15 @@ static void launchSlabKernel(hipStream_t stream, const SlabArgs<T>& a)
  * streams always carry the non-temporal hint here.
  * Same summation order as the type's gather / strip kernel (launchSlabFamily), so that the form AUTO settles on never
  * changes a bit of the result: 8-byte elements walk whole rows and consider the tail every 8 columns; fp32 keeps its
- * 8 phases x 2 columns; complex fp64 its 2 phases.  Otherwise a lane walks whole rows (PH 1) with 4 slab columns per
- * stage -- half the stage of the gather kernel: LDS gathers are short, and at 8 the kernel needs 148 VGPRs, which leaves
- * room for one 512-lane workgroup per CU only.  32 KiB of x per workgroup. */
+ * 8 phases x 2 columns; complex fp64 and the narrow form of every type their 2 phases.  The 8-byte types walk whole rows (PH 1) with 4
+ * slab columns per stage -- half the stage of the gather kernel: LDS gathers are short, and at 8 the kernel needs 148 VGPRs, which
+ * leaves room for one 512-lane workgroup per CU only.  32 KiB of x per workgroup. */
 template <typename T, int RPL, bool IS_HELL>
 static void launchTiled(hipStream_t stream, const SlabArgs<T>& a)
 {
-    constexpr int PH = sizeof(T) == 16 ? 2 : 1; /* the phases of the narrow kernels: whole-wave tail rows with one phase only */
+    /* RPL == 1 (a layout the wide kernels cannot read): the two phases x 4 columns of the narrow gather kernel, without tail rows, for every
+     * type -- XTILE on such a matrix gives the bits of GATHER on it (include/spgpu/tuning.h: the form never changes a bit) */
+    constexpr int PH = (sizeof(T) == 16 || RPL == 1) ? 2 : 1;
     if constexpr (sizeof(T) == 4 && RPL == 4)
         launchSlabKernel<T, RPL, 2 * RPL, IS_HELL, true, 2, true, true, false, 512, 32768>(stream, a);
     else if constexpr (sizeof(T) == 8 && RPL == 2)
