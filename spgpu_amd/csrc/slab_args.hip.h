@@ -6,6 +6,7 @@
  */
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
+#include "spmv_rules.h" /* kBlockThreads, kTailLanes, kTailUnroll */
 
 namespace spgpu {
 
@@ -56,11 +57,6 @@ template <typename T> struct SlabArgs {
     const unsigned short* planPacked; /* raggedSpmvKernel<..., PACKED>: a frozen matrix' column indices as 16-bit offsets from the block's
                                        * packBase, slot for slot as in rP (0xFFFF: ask rP); NULL: the matrix is not frozen */
 };
-
-constexpr int kBlockThreads = 256;
-constexpr int kTailLanes = 16; /* switch to whole-wave row processing when <= this many lanes are busy
-                                  (measured flat between 4 and 16 for the 1-phase kernel, worse above) */
-constexpr int kTailUnroll = 4; /* entries per lane in flight in tail mode */
 
 /* One lane registers a 32-row sub-group deeper than deepCap in the handle's deep list: an entry, and one item per
  * deepChunk columns beyond the cap.  Returns the entry, or -1 when the list is full -- the sub-group then stays with

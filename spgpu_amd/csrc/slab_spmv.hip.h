@@ -54,7 +54,7 @@ __device__ inline long long sampleGroup(long long groups, int q)
  * PH     phases: lane groups that split the entries of a row by k mod PH
  *        (PH == 1: a lane walks all entries of its rows, no cross-lane sum)
  * UNROLL slab-column loads issued back to back before the first gather
- * PIPE   the next stage is prefetched while the current one is consumed (every kernel but the lean one, launchLean)
+ * PIPE   the next stage is prefetched while the current one is consumed (every kernel but that of the Lean route, spmv_rules.h)
  * One wavefront owns 64/PH strips = (64/PH)*RPL consecutive rows.
  * STRIPS compiles the strip-load form in (see consume below); the form without it exists as well because the mere
  *        presence of the second loop costs the gather loop ~8 % on scattered matrices (measured; same instruction

@@ -467,7 +467,7 @@ def ragged_split(letter, step, deep_cap, asked=-1):
 
 def slab_shape(letter, form="gather", deep_cap=0, split=-1, deep_keep=None):
     """spmv_tail parameters of the kernel the library runs for (type, x form, deep split): csrc/ellpack_spmv.hip
-    launchSlabFamily / launchTiled, and with a deep cap the queue kernel (form "ragged").  None for the shapes without a
+    launchSlabFamily / the Tiled route of spmv_rules.h, and with a deep cap the queue kernel (form "ragged").  None for the shapes without a
     tail (complex fp64 outside the deep split: 2 phases)."""
     rpl = {"S": 4, "D": 2, "C": 2, "Z": 1}[letter]
     import os

@@ -1,8 +1,9 @@
-"""The ELL / HELL SpMV for rows as they come (spgpu_amd/csrc/ellpack_spmv.hip: launchSlabFamily -> launchRowsAsTheyCome, with
-slabSpmvKernel, sweepSpmvKernel and formProbeKernel), stated once for tests/test_gpu_spmv_shapes.py (which runs the cases on the
-GPU) and tests/test_spmv_launch_shapes.py (which checks on the CPU that the table reaches every instantiation and every named
-branch): the constants of the dispatch, the dispatch restated as a function of a call's arguments and addresses (wideLayout,
-launchSlabFamily, voteForm, launchRowsAsTheyCome, launchTiled, launchLean, launchSweep, launchFormProbe), the control flow
+"""The ELL / HELL SpMV for rows as they come (spgpu_amd/csrc/ellpack_spmv.hip: launchSlabFamily -> launchRowsAsTheyCome, on the
+rules of spgpu_amd/csrc/spmv_rules.h, with slabSpmvKernel, sweepSpmvKernel and formProbeKernel), stated once for
+tests/test_gpu_spmv_shapes.py (which runs the cases on the GPU), tests/test_spmv_launch_shapes.py (which checks on the CPU that the table
+reaches every instantiation and every named branch) and tests/test_spmv_dispatch.py (which runs the header itself against this
+restatement): the constants of the dispatch, the dispatch restated as a function of a call's arguments and addresses (spmv_rules.h:
+wideLayout, wideIO, callerForm, autoVote, chooseRoute, slabShape, sweepShape, probeShape, slabGrid, sweepGrid), the control flow
 of slabSpmvKernel and sweepSpmvKernel walked wavefront by wavefront, builders that place ELL and HELL matrices slot by slot, and
 the case table.  No torch, no library: importable everywhere.
 
@@ -15,7 +16,7 @@ index base holds NaN too: no product may use any of them.
 Left to tests/test_gpu_oell_device.py, which runs matrices of millions of rows anyway: the cap of 2 048 sweep workgroups and AUTO's
 2 Mi-row threshold for the SWEEP form."""
 import os
-import re
+import subprocess
 import zlib
 
 import numpy as np
@@ -23,20 +24,20 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "spgpu_amd", "csrc")
 
-# ---- the constants of the dispatch; source_constants() reads the same from the sources and the CPU test compares -----------------
-WAVE = 64                     # numeric.hip.h        kWave
-BLOCK = 256                   # slab_args.hip.h      kBlockThreads
-TAIL_LANES = 16               # slab_args.hip.h      kTailLanes
-TAIL_UNROLL = 4               # slab_args.hip.h      kTailUnroll
-TILE_BYTES = 32768            # ellpack_spmv.hip     launchTiled: every x tile
-TILED_BLOCK_S = 512           # ellpack_spmv.hip     launchTiled: the fp32 wide form's workgroup
-TAIL_EVERY = 8                # ellpack_spmv.hip     launchTiled / launchLean of the 8-byte types
-LEAN_MAX_HINT = 8             # ellpack_spmv.hip     launchRowsAsTheyCome: avgNnzPerRow in 1 .. 8
-LEAN_MAX_ELL = 16             # ellpack_spmv.hip     launchRowsAsTheyCome: ELL maxNnz <= 16
-SWEEP_LANE_ROWS = 32          # ellpack_spmv.hip     launchSweep: PACKS = 32 / VEC
-SWEEP_PACKS_16 = 16           # ellpack_spmv.hip     launchSweep: PACKS of 16-byte elements
-SWEEP_MAX_BLOCKS = 2048       # ellpack_spmv.hip     launchSweep
-AUTO_SWEEP_ROWS = 2 * 1024 * 1024   # ellpack_spmv.hip kAutoSweepRows
+# ---- the constants of the dispatch; header_constants() asks spmv_rules.h for the same and the CPU test compares ----------------------
+WAVE = 64                     # spmv_rules.h   kRulesWave (== numeric.hip.h kWave)
+BLOCK = 256                   # spmv_rules.h   kBlockThreads
+TAIL_LANES = 16               # spmv_rules.h   kTailLanes
+TAIL_UNROLL = 4               # spmv_rules.h   kTailUnroll
+TILE_BYTES = 32768            # spmv_rules.h   kTileBytes: every x tile
+TILED_BLOCK_S = 512           # spmv_rules.h   kTiledBlockFp32: the fp32 wide tile's workgroup
+TAIL_EVERY = 8                # spmv_rules.h   kTailEvery: the tiled and lean kernels of the 8-byte types
+LEAN_MAX_HINT = 8             # spmv_rules.h   kLeanMaxHint: avgNnzPerRow in 1 .. 8
+LEAN_MAX_ELL = 16             # spmv_rules.h   kLeanMaxEll: ELL maxNnz <= 16
+SWEEP_LANE_ROWS = 32          # spmv_rules.h   kSweepLaneRows: PACKS = 32 / VEC
+SWEEP_PACKS_16 = 16           # spmv_rules.h   kSweepPacks16: PACKS of 16-byte elements
+SWEEP_MAX_BLOCKS = 2048       # spmv_rules.h   kSweepMaxBlocks
+AUTO_SWEEP_ROWS = 2 * 1024 * 1024   # spmv_rules.h kAutoSweepRows
 SIZEOF = {"S": 4, "D": 8, "C": 8, "Z": 16}
 WIDE = {L: 16 // s for L, s in SIZEOF.items()}
 DTYPE = {"S": np.float32, "D": np.float64, "C": np.complex64, "Z": np.complex128}
@@ -46,35 +47,24 @@ AUTO, GATHER, STRIPS, XTILE, SWEEP = range(5)
 FORM_NAME = {AUTO: "auto", GATHER: "gather", STRIPS: "strips", XTILE: "xtile", SWEEP: "sweep"}
 
 
-def _read(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
+_PROGRAM = []
 
 
-def source_constants():
-    """The same constants as the sources state them (a regular expression per line that sets one)."""
-    args, disp, num = _read("slab_args.hip.h"), _read("ellpack_spmv.hip"), _read("numeric.hip.h")
-    one = lambda text, pattern: int(re.search(pattern, text).group(1))
-    tiled = re.search(r"static void launchTiled\(.*?\n}\n", disp, re.S).group(0)
-    lean = re.search(r"static void launchLean\(.*?\n}\n", disp, re.S).group(0)
-    sweep = re.search(r"static void launchSweep\(.*?\n}\n", disp, re.S).group(0)
-    rows = re.search(r"static void launchRowsAsTheyCome\(.*?\n}\n", disp, re.S).group(0)
-    return dict(
-        WAVE=one(num, r"constexpr int kWave = (\d+);"),
-        BLOCK=one(args, r"constexpr int kBlockThreads = (\d+);"),
-        TAIL_LANES=one(args, r"constexpr int kTailLanes = (\d+);"),
-        TAIL_UNROLL=one(args, r"constexpr int kTailUnroll = (\d+);"),
-        TILE_BYTES=sorted({int(m) for m in re.findall(r"(?:256|512), (\d+)(?:, \d+)?>\(stream, a\)", tiled)}),
-        TILED_BLOCK_S=one(tiled, r"sizeof\(T\) == 4 && RPL == 4\)\s*\n\s*launchSlabKernel<[^>]*?, (\d+), \d+>"),
-        TAIL_EVERY=sorted({one(tiled, r"256, 32768, (\d+)>"), one(lean, r"kBlockThreads, 0, (\d+)>")}),
-        LEAN_MAX_HINT=one(rows, r"a\.avgNnzPerRow <= (\d+)"),
-        LEAN_MAX_ELL=one(rows, r"a\.maxNnz <= (\d+)"),
-        SWEEP_LANE_ROWS=one(sweep, r": (\d+) / VEC;"),
-        SWEEP_PACKS_16=one(sweep, r"sizeof\(T\) == 16 \? (\d+) :"),
-        SWEEP_MAX_BLOCKS=one(sweep, r"blocks > (\d+) \?"),
-        AUTO_SWEEP_ROWS=eval(re.search(r"constexpr int kAutoSweepRows = ([\d *]+);", disp).group(1)),
-        TILE_SPAN=re.search(r"a\.tileSpanLimit = \(long long\)\((\d+) / sizeof\(T\)\) \* (\d+) / (\d+);", disp).groups(),
-    )
+def dispatch_program(directory):
+    """tests/spmv_dispatch_cases.cpp, the stand-alone program around spgpu_amd/csrc/spmv_rules.h, built into `directory` with the
+    undefined-behaviour sanitizer (once per process): the path of the executable."""
+    if not _PROGRAM:
+        exe = os.path.join(str(directory), "spmv_dispatch_cases")
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
+                        os.path.join(ROOT, "tests", "spmv_dispatch_cases.cpp"), "-o", exe], check=True)
+        _PROGRAM.append(exe)
+    return _PROGRAM[0]
+
+
+def header_constants(program):
+    """name -> value, as the program's constants mode prints what spmv_rules.h states."""
+    done = subprocess.run([program, "constants"], capture_output=True, text=True, check=True)
+    return {name: int(value) for name, value in (line.split() for line in done.stdout.splitlines())}
 
 
 # ---- the dispatch restated -------------------------------------------------------------------------------------------------------
@@ -120,7 +110,7 @@ def wide_layout(letter, hell, rows, hack, val_stride, idx_stride, cM, rP):
 
 
 def tiled_kernel(letter, rpl, hell):
-    """launchTiled<T, RPL, IS_HELL>."""
+    """slabShape of the Tiled (rpl > 1) and NarrowTiled routes."""
     ph = 2 if SIZEOF[letter] == 16 or rpl == 1 else 1          # narrow: the order of the narrow gather kernel
     if SIZEOF[letter] == 4 and rpl == 4:
         return slab(letter, rpl, 2 * rpl, hell, 2, True, True, False, TILED_BLOCK_S, TILE_BYTES)
@@ -155,7 +145,7 @@ FIRST_CALL = dict(strips=True, tile=False, sweep=False, probe=False)
 
 
 def vote_form(letter, rows, said, calls):
-    """voteForm under AUTO for an eligible call (wide layout, more than one row per lane, no x tile asked for).  said: what the three
+    """autoVote (voteForm) under AUTO for an eligible call (wide layout, more than one row per lane, no x tile asked for).  said: what the three
     sample words hold for this matrix (0 nothing yet, 1 scattered, 2 strips, 3 inside a window, 4 a matrix for SWEEP); calls: the
     calls on this (rP, rows) before this one (0: the record is new, its words are zero)."""
     gathers, local, sweeps = said.count(1), said.count(3), said.count(4)
@@ -166,7 +156,7 @@ def vote_form(letter, rows, said, calls):
 
 
 def form_probe(letter, hell, wide_ok):
-    """launchFormProbe: formProbeKernel's template arguments T, RPL, PH, IS_HELL, STEP; three workgroups of one wavefront."""
+    """launchFormProbe (probeShape): formProbeKernel's template arguments T, RPL, PH, IS_HELL, STEP; three workgroups of one wavefront."""
     w = WIDE[letter]
     if w > 1 and wide_ok:
         return ("probe", letter, w, 2 * w, bool(hell), 2 * w * 2) if SIZEOF[letter] == 4 else ("probe", letter, w, 1, bool(hell), 8)
@@ -180,7 +170,7 @@ def every_probe(letter, hell):
 
 
 def dispatch(letter, hell, form, rows, hack, val_stride, idx_stride, max_nnz, avg, addr, has_beta, vote=None):
-    """launchSlabFamily for rIdx == NULL, Run, nothing adopted or frozen, SPGPU_X_STRIPS unset.  addr: the addresses of cM, rP, z, y
+    """launchSlabFamily (callerForm, chooseRoute) for rIdx == NULL, Run, nothing adopted or frozen, SPGPU_X_STRIPS unset.  addr: the addresses of cM, rP, z, y
     (y: None for NULL).  vote: under AUTO what vote_form answers; a first call on a matrix is FIRST_CALL.
     Returns dict(kernel, wide_io, grid, noted: the form spgpuGetLastSpmvForm reports, wide_ok, fails, probe: the formProbeKernel
     launched in front of the kernel, or None)."""

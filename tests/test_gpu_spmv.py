@@ -279,7 +279,7 @@ def test_sweep_form_is_the_one_phase_order(gpu, letter, fmt, n, hack, base):
 @pytest.mark.parametrize("letter", ["D", "C"])
 @pytest.mark.parametrize("hint", [1, 5, 8])
 def test_short_row_hint_same_bits(gpu, letter, hint):
-    """avgNnzPerRow in 1 .. 8 selects the kernel without a prefetch ring for the 8-byte types (ellpack_spmv.hip launchLean; the
+    """avgNnzPerRow in 1 .. 8 selects the kernel without a prefetch ring for the 8-byte types (spmv_rules.h: the Lean route; the
     hint is the reference's own, hell_spmv_base_template.cuh:306-325, and only an average): on rows of 0 .. 300 entries, empty
     rows, rows longer than a stage and long enough for the whole-wave tail, HELL and ELL (ELL with maxNnzPerRow <= 16 takes the
     kernel, the long one keeps the prefetching kernel), beta != 0 and in place -- the bytes of the default kernel (hint 0) and

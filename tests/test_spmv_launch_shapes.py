@@ -1,6 +1,6 @@
 """CPU: the case table of tests/test_gpu_spmv_shapes.py (tests/spmv_launch_shapes.py) is what that module needs it to be -- the
-constants equal the sources', the table names every instantiation the rIdx == NULL dispatch can select for every type and both
-formats, each with a case of more than one workgroup, voteForm and launchFormProbe restated give AUTO's sequence, every case takes the route its name claims and the branches it is in the table for (the kernels' control flow walked on
+constants equal the sources' (spmv_rules.h, asked through tests/spmv_dispatch_cases.cpp), the table names every instantiation the rIdx == NULL dispatch can select for every type and both
+formats, each with a case of more than one workgroup, autoVote and launchFormProbe restated give AUTO's sequence, every case takes the route its name claims and the branches it is in the table for (the kernels' control flow walked on
 the CPU), every named branch is reached per type, and on every matrix the oracle, reading the NaN-poisoned arrays in the order of
 the case's kernel, returns no NaN and keeps exact_ref's bound of the extended-precision sums: the host half of the GPU module's
 assertions, without a GPU.
@@ -31,16 +31,25 @@ NEVER = {
 }
 
 
-def test_constants_equal_the_sources():
-    src = M.source_constants()
-    assert src["WAVE"] == M.WAVE and src["BLOCK"] == M.BLOCK
-    assert src["TAIL_LANES"] == M.TAIL_LANES and src["TAIL_UNROLL"] == M.TAIL_UNROLL
-    assert src["TILE_BYTES"] == [M.TILE_BYTES] and src["TILED_BLOCK_S"] == M.TILED_BLOCK_S
-    assert src["TAIL_EVERY"] == [M.TAIL_EVERY]
-    assert src["LEAN_MAX_HINT"] == M.LEAN_MAX_HINT and src["LEAN_MAX_ELL"] == M.LEAN_MAX_ELL
-    assert src["SWEEP_LANE_ROWS"] == M.SWEEP_LANE_ROWS and src["SWEEP_PACKS_16"] == M.SWEEP_PACKS_16
-    assert src["SWEEP_MAX_BLOCKS"] == M.SWEEP_MAX_BLOCKS and src["AUTO_SWEEP_ROWS"] == M.AUTO_SWEEP_ROWS
-    assert src["TILE_SPAN"] == (str(M.TILE_BYTES), "5", "4")
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    return M.dispatch_program(tmp_path_factory.mktemp("spmv_dispatch"))
+
+
+def test_constants_equal_the_sources(program):
+    """The sources' side is spmv_rules.h itself, asked through tests/spmv_dispatch_cases.cpp (ellpack_spmv.hip asserts kRulesWave == kWave)."""
+    src = M.header_constants(program)
+    assert src["kRulesWave"] == M.WAVE and src["kBlockThreads"] == M.BLOCK
+    assert src["kTailLanes"] == M.TAIL_LANES and src["kTailUnroll"] == M.TAIL_UNROLL
+    assert src["kTileBytes"] == M.TILE_BYTES and src["kTiledBlockFp32"] == M.TILED_BLOCK_S
+    assert src["kTailEvery"] == M.TAIL_EVERY
+    assert src["kLeanMaxHint"] == M.LEAN_MAX_HINT and src["kLeanMaxEll"] == M.LEAN_MAX_ELL
+    assert src["kSweepLaneRows"] == M.SWEEP_LANE_ROWS and src["kSweepPacks16"] == M.SWEEP_PACKS_16
+    assert src["kSweepMaxBlocks"] == M.SWEEP_MAX_BLOCKS and src["kAutoSweepRows"] == M.AUTO_SWEEP_ROWS
+    assert (src["kTileBytes"], src["kTileSpanNum"], src["kTileSpanDen"]) == (M.TILE_BYTES, 5, 4)
+    assert [src[f"tileSpanLimit{s}"] for s in (4, 8, 16)] == [M.TILE_BYTES // s * 5 // 4 for s in (4, 8, 16)]
+    assert [src[k] for k in ("kFormAuto", "kFormGather", "kFormStrips", "kFormXtile", "kFormSweep")] == [M.AUTO, M.GATHER, M.STRIPS, M.XTILE, M.SWEEP]
+    assert all(src[f"wideGroupRows{M.SIZEOF[L]}"] == M.group_rows(L) for L in "SDC")
     # the oracle's own statement of the default kernels' shapes
     for L in "SDC":
         ph, unroll = (8, 2) if L == "S" else (1, 8)
@@ -78,7 +87,7 @@ def test_dispatch_restated_on_a_few_hand_worked_calls():
 
 
 def test_vote_and_probe_restated_on_the_auto_sequence():
-    """voteForm and launchFormProbe: a new record votes strips and launches no probe; two samples of three decide; a form that does
+    """autoVote (voteForm) and launchFormProbe: a new record votes strips and launches no probe; two samples of three decide; a form that does
     not report itself gets the three-wavefront probe with its first call and every fourth."""
     assert M.vote_form("D", 708, [0, 0, 0], 0) == M.FIRST_CALL
     assert M.vote_form("D", 708, [2, 2, 3], 1) == dict(strips=True, tile=False, sweep=False, probe=False)
