@@ -164,6 +164,21 @@ void spgpuDestroy(spgpuHandle_t pHandle)
     free(h);
 }
 
+void* spgpuDeviceAlloc(spgpuHandle_t pHandle, size_t bytes)
+{
+    void* memory = NULL;
+    int previous = 0;
+    (void)hipGetDevice(&previous);
+    (void)hipSetDevice(pHandle->device);
+    const hipError_t allocated = hipMalloc(&memory, bytes);
+    (void)hipSetDevice(previous);
+    if (allocated != hipSuccess) {
+        (void)hipGetLastError();
+        return NULL;
+    }
+    return memory;
+}
+
 void spgpuStreamCreate(spgpuHandle_t pHandle, hipStream_t* stream)
 {
     int previous = 0;

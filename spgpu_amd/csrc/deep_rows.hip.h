@@ -19,7 +19,7 @@
  * and never a bit of the result.
  */
 
-constexpr int kPlanDeepMost = 8; /* sub-groups one batch holds (their tables live in LDS) */
+/* kPlanDeepMost (ordered_rules.h, where the planned grid is counted with it): sub-groups one batch holds (their tables live in LDS) */
 
 struct ChunkPlan {
     int mainChunks; /* pieces of the walked part */

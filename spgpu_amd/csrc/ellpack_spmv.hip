@@ -118,8 +118,8 @@ static bool attachDeepList(spgpuHandle_t handle, SlabArgs<T>& a, bool wideOk, Sp
     return true;
 }
 
-/* Which of the queue kernel's two product shapes (launchRagged)?  orderedProbeKernel answers; the answer is kept with AUTO's
- * per-matrix words and read without synchronisation: a first call runs the 1 024-row shape, which is never far off.
+/* Which of the queue kernel's two product shapes (ordered_rules.h: queueShape)?  orderedProbeKernel answers; the answer is kept with
+ * AUTO's per-matrix words and read without synchronisation: a first call runs the 1 024-row shape, which is never far off.
  * wait (Prepare, Freeze): a first call waits for the answer a second call would have found. */
 template <typename T, bool IS_HELL>
 static int orderedShape(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& a, bool wait)
@@ -127,43 +127,37 @@ static int orderedShape(spgpuHandle_t handle, hipStream_t stream, const SlabArgs
     int calls = 0, tag = 0;
     int* seen = spgpuFormFeedback(handle, a.rP, a.rows, &calls, &tag);
     int said = spgpuFeedbackSaid(((volatile int*)seen)[3], tag);
-    if (said == 0 || calls % 64 == 0)
+    if (reprobe(said, calls))
         hipLaunchKernelGGL((orderedProbeKernel<IS_HELL>), dim3(1), dim3(kWave), 0, stream, a.rP, a.rS, a.hackOffsets, a.rIdx, a.hackSize,
                            a.idxStride, a.maxNnz, a.rows, a.baseIndex, seen + 3, tag);
     if (wait && said == 0 && hipStreamSynchronize(stream) == hipSuccess)
         said = spgpuFeedbackSaid(((volatile int*)seen)[3], tag);
-    return said == 4 || said == 6 ? 4 : 0; /* 6: the blocks are the windows of an aligned order */
+    return orderedShapeSaid(said);
 }
 
-/* The ordered path: the queue-driven kernel for rows ordered by length (ragged_spmv.hip.h); x through an LDS tile unless the
- * caller asked for plain gathers.  A matrix seen before has a plan (planned_spmv.hip): one launch, the deep sub-groups in
- * workgroups of their own, no list.  Otherwise the queue kernel registers them in the stream's deep list and the deep kernels
- * follow.  noDeepList: this stream of the handle has no deep list (every list belongs to a stream with work in flight, or the
+/* The ordered path: the queue-driven kernel for rows ordered by length (ragged_spmv.hip.h), every choice by ordered_rules.h; x through
+ * an LDS tile unless the caller asked for plain gathers.  A matrix seen before has a plan (planned_spmv.hip): one launch, the deep
+ * sub-groups in workgroups of their own, no list.  Otherwise the queue kernel registers them in the stream's deep list and the deep
+ * kernels follow.  noDeepList: this stream of the handle has no deep list (every list belongs to a stream with work in flight, or the
  * allocation failed): the same kernel family without any state -- the matrix' plan if it is ready, else no plan at all (every
  * deep sub-group worked off by its own block).  Same bits in every case.
  * Returns, for Prepare / Freeze: the next SpMV on these arrays runs from a plan / the matrix is frozen. */
 template <typename T, bool IS_HELL>
 static bool launchOrdered(spgpuHandle_t handle, hipStream_t stream, SlabArgs<T>& a, int form, const SpgpuDeepList& list, bool noDeepList, SpmvCall call)
 {
-    constexpr int WIDE = wideOf(sizeof(T));
-    const bool tiledForm = form != SPGPU_SPMV_FORM_GATHER;
+    const bool tiledForm = form != SPGPU_SPMV_FORM_GATHER, rowOrder = a.rIdx != nullptr;
     spgpuNoteSpmvForm(handle, tiledForm ? SPGPU_SPMV_FORM_XTILE : SPGPU_SPMV_FORM_GATHER);
-    int shape = spgpuTuning()->raggedShape;
-    if (shape == 0 && tiledForm && a.rIdx != nullptr && sizeof(T) <= 8)
-        shape = orderedShape<T, IS_HELL>(handle, stream, a, call != SpmvCall::Run);
-    if (noDeepList && shape != 4)
-        shape = 0;
-    const bool plannable = !tiledForm || shape == 0 || shape == 4;
+    const int knob = spgpuTuning()->raggedShape;
+    const int probed = probesShape(knob, tiledForm, rowOrder, sizeof(T)) ? orderedShape<T, IS_HELL>(handle, stream, a, call != SpmvCall::Run) : 0;
+    const int shape = orderedShapeFor(knob, tiledForm, rowOrder, sizeof(T), probed, noDeepList);
+    const bool planned = plannable(tiledForm, shape);
     if (call != SpmvCall::Run)
-        return plannable && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, false, call);
-    if (plannable && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, noDeepList, SpmvCall::Run))
+        return planned && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, false, call);
+    if (planned && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, noDeepList, SpmvCall::Run))
         return true;
-    /* ELL says how long its longest row is: when none can exceed the cap nothing registers and the two launches behind
-     * the main kernel (~5 us each when empty) are left out; HELL does not say */
-    const bool deepPossible = IS_HELL || a.maxNnz > a.deepCap;
-    const bool deepKernels = launchRagged<T, WIDE, IS_HELL, true>(stream, a, shape, tiledForm);
-    if (deepPossible && deepKernels)
-        launchDeep<T, WIDE, IS_HELL>(stream, a);
+    launchRagged<T, IS_HELL>(stream, a, shape, tiledForm);
+    if (deepKernelsFollow(IS_HELL, a.maxNnz, a.deepCap))
+        launchDeep<T, wideOf(sizeof(T)), IS_HELL>(stream, a);
     if (list.idle) {
         /* complete = the list has no user (core.c: a list may change hands) -- unless this launch is being captured: a graph
          * carries the list's addresses and may be replayed at any time, so the list stays with this stream for good */

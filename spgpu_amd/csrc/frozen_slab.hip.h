@@ -91,12 +91,9 @@ static bool freezeSlab(spgpuHandle_t handle, hipStream_t stream, const SpgpuSpmv
     bool frozen = plan && plan->packed && plan->state == SPGPU_PLAN_READY;
     if (plan && !frozen && plan->state != SPGPU_PLAN_GIVEN_UP) {
         const long long groups = ((long long)key.rows + groupRows - 1) / groupRows;
-        const size_t baseBytes = ((size_t)groups * sizeof(int) + 255) / 256 * 256;
-        void *device = nullptr, *packed = nullptr;
-        int previous = 0;
-        (void)hipGetDevice(&previous);
-        (void)hipSetDevice(handle->device);
-        bool ok = hipMalloc(&device, baseBytes + 256) == hipSuccess;
+        const size_t baseBytes = roundUpTo((size_t)groups * sizeof(int), 256);
+        void *device = spgpuDeviceAlloc(handle, baseBytes + 256), *packed = nullptr;
+        bool ok = device != nullptr;
         unsigned long long* counts = ok ? reinterpret_cast<unsigned long long*>(static_cast<char*>(device) + baseBytes) : nullptr;
         unsigned long long said[2] = {0, 0};
         long long slots = IS_HELL ? 0 : key.idxStride * (long long)key.maxNnz;
@@ -107,22 +104,20 @@ static bool freezeSlab(spgpuHandle_t handle, hipStream_t stream, const SpgpuSpmv
             slots = (long long)said[0];
         }
         ok = ok && slots > 0;
-        const size_t packedBytes = ok ? ((size_t)slots * sizeof(unsigned short) + 255) / 256 * 256 : 0;
-        ok = ok && hipMalloc(&packed, packedBytes) == hipSuccess;
-        (void)hipSetDevice(previous);
+        const size_t copyBytes = ok ? packedBytes(slots) : 0;
+        ok = ok && (packed = spgpuDeviceAlloc(handle, copyBytes)) != nullptr;
         if (ok) {
             if (spgpuTuning()->poisonScratch)
-                (void)hipMemsetAsync(packed, 0xA5, packedBytes, stream);
+                (void)hipMemsetAsync(packed, 0xA5, copyBytes, stream);
             (void)hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), stream);
             hipLaunchKernelGGL((slabPackKernel<IS_HELL>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, stream, rP, rS, hackOffsets, key.hackSize,
                                key.idxStride, key.maxNnz, key.rows, key.baseIndex, groupRows, static_cast<int*>(device), static_cast<unsigned short*>(packed), counts);
             ok = hipMemcpyAsync(said, counts, sizeof(said), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
         }
-        const int mostPct = spgpuTuning()->freezeEscapesPct < 0 ? 0 : spgpuTuning()->freezeEscapesPct;
-        if (ok && said[1] * 100ull <= said[0] * (unsigned long long)mostPct) { /* at most one escape in a hundred entries (SPGPU_FREEZE_MAX_ESCAPES_PCT) */
+        if (ok && keepsCopy(said[0], said[1], spgpuTuning()->freezeEscapesPct)) { /* at most one escape in a hundred entries (SPGPU_FREEZE_MAX_ESCAPES_PCT) */
             plan->device = device;
             plan->packed = packed;
-            plan->packedBytes = (long long)packedBytes;
+            plan->packedBytes = (long long)copyBytes;
             plan->blocks = 0;
             plan->deep = 0;
             plan->uses = 0;

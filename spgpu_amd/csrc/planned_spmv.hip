@@ -10,8 +10,10 @@
  *     sub-groups; their number goes to a pinned word).  Started on the SpMV's stream by the first call that sees the matrix,
  *     never waited for: the call itself, and every later one until the analysis' event has completed, runs the path
  *     without a plan (registration in the stream's deep list, two launches behind the main kernel: ellpack_spmv.hip).
- *   - the launch with a plan: raggedSpmvKernel<..., PLAN> (ragged_spmv.hip.h) over planMainBlocks + ceil(deep / G)
- *     workgroups -- ONE launch, no list, nothing behind it.
+ *   - the launch with a plan: raggedSpmvKernel<..., PLAN> (ragged_spmv.hip.h) over planGrid workgroups -- ONE launch, no list,
+ *     nothing behind it.
+ * The kernel shape a plan is made for, that grid, the layout of the plan's buffer and every decision of the state machine (stale, given
+ * up, may be packed, keeps its copy) are stated once in ordered_rules.h; here are the kernels, the records and the launches.
  * Both paths add every row's products in the same order (deep_rows.hip.h: chunksOf), so which of them a call takes -- first
  * call, settled, stale plan, captured graph (planned only where the plan is held, include/spgpu/ext/graph.h: a graph outlives a
  * plan the host may retire) -- does not change a bit of z.
@@ -233,6 +235,8 @@ __global__ __launch_bounds__(256) void planPackKernel(const int* __restrict__ rP
     }
 }
 
+constexpr size_t kPackCounterBytes = 256; /* entries and escapes as planPackKernel counts them, behind the copy in the same allocation */
+
 /* Lock held, plan READY.  Builds the plan's 16-bit index copy on `stream` and waits for it.  False: no memory, or a launch failed
  * (the plan stays as it is, unfrozen). */
 template <bool IS_HELL>
@@ -253,38 +257,27 @@ static bool packPlan(SpgpuSpmvPlan* plan, spgpuHandle_t handle, hipStream_t stre
     }
     if (slots <= 0)
         return false;
-    const size_t bytes = ((size_t)slots * sizeof(unsigned short) + 255) / 256 * 256 + 256; /* (a lane's last pack may reach past the last real slot's word; + the two counters) */
-    void* packed = nullptr;
-    int previous = 0;
-    (void)hipGetDevice(&previous);
-    (void)hipSetDevice(handle->device);
-    const hipError_t allocated = hipMalloc(&packed, bytes);
-    (void)hipSetDevice(previous);
-    if (allocated != hipSuccess) {
-        (void)hipGetLastError();
+    const size_t bytes = packedBytes(slots) + kPackCounterBytes;
+    void* packed = spgpuDeviceAlloc(handle, bytes);
+    if (!packed)
         return false;
-    }
     if (spgpuTuning()->poisonScratch) /* testing: no word is read that the pack kernel has not written */
         (void)hipMemsetAsync(packed, 0xA5, bytes, stream);
     SpgpuPlanBlock* records = static_cast<SpgpuPlanBlock*>(plan->device);
     unsigned short* words = static_cast<unsigned short*>(packed);
-    unsigned long long* counts = reinterpret_cast<unsigned long long*>(static_cast<char*>(packed) + bytes - 256);
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(static_cast<char*>(packed) + bytes - kPackCounterBytes);
     (void)hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), stream);
-    if (plan->subs == 64)
-        hipLaunchKernelGGL((planPackKernel<IS_HELL, 64>), dim3((unsigned)plan->blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
+    withPlanSubs<false>(plan->subs, [&](auto subs) {
+        hipLaunchKernelGGL((planPackKernel<IS_HELL, decltype(subs)::value>), dim3((unsigned)plan->blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
                            plan->idxStride, plan->maxNnz, plan->rows, plan->baseIndex, records, words, counts);
-    else
-        hipLaunchKernelGGL((planPackKernel<IS_HELL, 32>), dim3((unsigned)plan->blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
-                           plan->idxStride, plan->maxNnz, plan->rows, plan->baseIndex, records, words, counts);
+    });
     unsigned long long said[2] = {0, 0};
     if (hipMemcpyAsync(said, counts, sizeof(said), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(packed);
         return false;
     }
-    /* scattered columns: the copy would save nothing (an escape costs its rP word on top of the 16-bit one) -- the matrix keeps its
-     * plan, unfrozen */
-    if (said[1] * 100ull > said[0] * (unsigned long long)(spgpuTuning()->freezeEscapesPct < 0 ? 0 : spgpuTuning()->freezeEscapesPct)) {
+    if (!keepsCopy(said[0], said[1], spgpuTuning()->freezeEscapesPct)) { /* scattered columns: the matrix keeps its plan, unfrozen */
         (void)hipFree(packed);
         return false;
     }
@@ -293,22 +286,28 @@ static bool packPlan(SpgpuSpmvPlan* plan, spgpuHandle_t handle, hipStream_t stre
     return true;
 }
 
-/* ---- host ---------------------------------------------------------------------------------------------------------- */
+/* ---- host: shapes, grids, the buffer's layout and every yes / no below are ordered_rules.h's --------------------------------------- */
+static_assert(sizeof(SpgpuPlanBlock) == kPlanRecordBytes, "ordered_rules.h lays the plan's buffer out for another record");
 
-/* Wave-wide loads per stage of the PACKED kernels beyond the unpacked kernels' (kRaggedUnroll).  A stage of the queue kernel
+/* Wave-wide loads per stage of the PACKED kernels: the unpacked kernels' (kRaggedUnroll), no more.  A stage of the queue kernel
  * is a memory round trip and a stage with 16-bit indices is a sixth smaller, so the same bytes in flight could be a third more
  * columns per round trip; the order of additions would not depend on it (a phase adds its columns in ascending order whatever
- * the stage size; the chunks of a split sub-group are sized by the unpacked kernels' stage, raggedSplit).  MEASURED with 1
+ * the stage size; the chunks of a split sub-group are sized by the unpacked kernels' stage, raggedSplit).  MEASURED with 1 more
  * (fp64: 4 loads per stage): 36-44 bytes of scratch per lane, and the target goes from 0.68-0.72 to 0.80-0.83 ms (band) -- a
  * spill is re-read behind a vmcnt(0) wait, which drains the prefetch at every item.  Consuming the stage in two halves (8 x values
- * alive instead of 16) leaves the scratch where it is: the ring of three stages is what does not fit.  0 it stays.
+ * alive instead of 16) leaves the scratch where it is: the ring of three stages is what does not fit.  None it stays.
  * Workgroups of 6 wavefronts at 3 per SIMD (168 VGPRs: 4 or 5 loads per stage without scratch) instead: 0.66-0.70 -> 1.01-1.05 ms
  * on the frozen target -- fewer, longer-lived wavefronts lose more than the deeper stage wins.  Not kept either. */
-constexpr int kPackedMoreUnroll = 0;
 
-static size_t roundUp16(size_t v)
+/* The parts of a plan's device buffer. */
+struct PlanPointers {
+    SpgpuPlanBlock* blocks;
+    int *counts, *deepSubs;
+};
+static PlanPointers planPointers(void* device, const PlanLayout& at)
 {
-    return (v + 15) / 16 * 16;
+    char* base = static_cast<char*>(device);
+    return {reinterpret_cast<SpgpuPlanBlock*>(base), reinterpret_cast<int*>(base + at.blockBytes), reinterpret_cast<int*>(base + at.blockBytes + at.countBytes)};
 }
 
 /* Lock held.  Starts the analysis of the record's matrix on `stream`; the record is BUILDING afterwards (EMPTY if the
@@ -317,44 +316,28 @@ template <bool IS_HELL>
 static void startPlan(spgpuHandle_t handle, SpgpuSpmvPlan* plan, hipStream_t stream)
 {
     SpgpuPrivateHandle* h = spgpuPrivate(handle);
-    const long long subs = ((long long)plan->rows + 31) / 32;
-    const int blocks = (int)((subs + plan->subs - 1) / plan->subs);
-    const size_t blockBytes = roundUp16((size_t)blocks * sizeof(SpgpuPlanBlock)), countBytes = roundUp16((size_t)blocks * sizeof(int));
-    void* device = nullptr;
-    int previous = 0;
-    (void)hipGetDevice(&previous); /* the plan lives where the handle's streams run, whatever device the caller has current */
-    (void)hipSetDevice(handle->device);
-    const hipError_t allocated = hipMalloc(&device, blockBytes + countBytes + (size_t)subs * sizeof(int));
-    (void)hipSetDevice(previous);
-    if (allocated != hipSuccess) {
-        (void)hipGetLastError();
+    const int blocks = (int)queueGrid(plan->rows, plan->subs);
+    const PlanLayout layout = planLayout(blocks, subGroupsOf(plan->rows), kPlanRecordBytes);
+    void* device = spgpuDeviceAlloc(handle, layout.total); /* the plan lives where the handle's streams run */
+    if (!device) {
         plan->state = SPGPU_PLAN_EMPTY;
         return;
     }
     if (spgpuTuning()->poisonScratch) /* testing: the analysis must write every word a launch reads */
-        (void)hipMemsetAsync(device, 0xFF, blockBytes + countBytes + (size_t)subs * sizeof(int), stream);
+        (void)hipMemsetAsync(device, 0xFF, layout.total, stream);
     plan->device = device;
     plan->blocks = blocks;
     plan->deep = 0;
     plan->uses = 0;
     plan->pinned[0] = 0;
     plan->pinned[1] = 0;
-    SpgpuPlanBlock* blockRecords = static_cast<SpgpuPlanBlock*>(device);
-    int* counts = reinterpret_cast<int*>(static_cast<char*>(device) + blockBytes);
-    int* deepSubs = reinterpret_cast<int*>(static_cast<char*>(device) + blockBytes + countBytes);
-    const int* rP = static_cast<const int*>(plan->rP);
-    const int* rS = static_cast<const int*>(plan->rS);
-    const int* hackOffsets = static_cast<const int*>(plan->hackOffsets);
-    if (plan->subs == 64)
-        hipLaunchKernelGGL((planBlocksKernel<IS_HELL, 64>), dim3((unsigned)blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
-                           plan->idxStride, plan->maxNnz, plan->rows, plan->baseIndex, plan->deepCap, blockRecords, counts);
-    else if (plan->subs == 16)
-        hipLaunchKernelGGL((planBlocksKernel<IS_HELL, 16>), dim3((unsigned)blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
-                           plan->idxStride, plan->maxNnz, plan->rows, plan->baseIndex, plan->deepCap, blockRecords, counts);
-    else
-        hipLaunchKernelGGL((planBlocksKernel<IS_HELL, 32>), dim3((unsigned)blocks), dim3(256), 0, stream, rP, rS, hackOffsets, plan->hackSize,
-                           plan->idxStride, plan->maxNnz, plan->rows, plan->baseIndex, plan->deepCap, blockRecords, counts);
-    hipLaunchKernelGGL(planListKernel, dim3(1), dim3(1024), 0, stream, blockRecords, counts, blocks, plan->subs, deepSubs, plan->pinned);
+    const PlanPointers at = planPointers(device, layout);
+    withPlanSubs<true>(plan->subs, [&](auto subs) {
+        hipLaunchKernelGGL((planBlocksKernel<IS_HELL, decltype(subs)::value>), dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const int*>(plan->rP),
+                           static_cast<const int*>(plan->rS), static_cast<const int*>(plan->hackOffsets), plan->hackSize, plan->idxStride, plan->maxNnz,
+                           plan->rows, plan->baseIndex, plan->deepCap, at.blocks, at.counts);
+    });
+    hipLaunchKernelGGL(planListKernel, dim3(1), dim3(1024), 0, stream, at.blocks, at.counts, blocks, plan->subs, at.deepSubs, plan->pinned);
     if (hipEventRecord(plan->built, stream) != hipSuccess) {
         (void)hipGetLastError();
         spgpuPlanRetire(handle, plan); /* (the kernels may run: the buffer waits in the graveyard) */
@@ -365,11 +348,79 @@ static void startPlan(spgpuHandle_t handle, SpgpuSpmvPlan* plan, hipStream_t str
     h->planBuilds += 1;
 }
 
+/* The plan fields of the arguments as a launch with NO plan reads them: nothing is listed, no x tile, no 16-bit copy. */
+template <typename T>
+static SlabArgs<T> unplannedArgs(const SlabArgs<T>& in, int subs)
+{
+    SlabArgs<T> a = in;
+    a.split = raggedSplit(sizeof(T), a.deepCap, spgpuTuning()->raggedSplit);
+    a.deepHeader = nullptr;
+    a.planBlocks = nullptr;
+    a.planDeepSubs = nullptr;
+    a.planDeep = 0;
+    a.planFlags = nullptr;
+    a.planPacked = nullptr;
+    a.planDeepPerBlock = kPlanDeepMost;
+    a.planDeepStride = 0;
+    a.planMainBlocks = (int)queueGrid(a.rows, subs);
+    return a;
+}
+
+/* ... and as a launch from a READY plan reads them. */
+template <typename T>
+static void attachPlan(SlabArgs<T>& a, const SpgpuSpmvPlan* plan, bool tiled)
+{
+    const PlanPointers at = planPointers(plan->device, planLayout(plan->blocks, subGroupsOf(plan->rows), kPlanRecordBytes));
+    a.planBlocks = at.blocks;
+    a.planDeepSubs = at.deepSubs;
+    a.planDeep = plan->deep;
+    a.planMainBlocks = plan->blocks;
+    a.planFlags = plan->pinned;
+    if (packedKernels(tiled, sizeof(T)))
+        a.planPacked = static_cast<const unsigned short*>(plan->packed); /* a frozen matrix: 16-bit indices */
+}
+
+/* raggedSpmvKernel<..., PLAN> over the blocks of rows and the workgroups of deep sub-groups. */
+template <typename T, bool IS_HELL>
+static void launchWithPlan(hipStream_t stream, SlabArgs<T>& a, bool tiled, bool staged)
+{
+    const unsigned grid = planGrid(a.planMainBlocks, a.planDeep);
+    a.planDeepStride = planDeepStride(grid, planDeepBlocks(a.planDeep));
+    withConstants([&](auto gather, auto packed, auto stagedToo) {
+        if constexpr (!packed || packedKernels(!gather, sizeof(T)))
+            launchQueue<T, IS_HELL, !gather, stagedToo, true, packed>(stream, grid, a);
+    }, !tiled, a.planPacked != nullptr, staged);
+}
+
+/* Lock held.  The matrix' record as this call finds it: looked up (in a capture: a held one only, never made), landed if its analysis
+ * has completed, retired if a kernel found it stale, and -- EMPTY -- its analysis started.  NULL: the call runs without a plan. */
+template <bool IS_HELL>
+static SpgpuSpmvPlan* currentPlan(spgpuHandle_t handle, hipStream_t stream, const SpgpuSpmvPlan& key, bool heldOnly)
+{
+    SpgpuPrivateHandle* h = spgpuPrivate(handle);
+    SpgpuSpmvPlan* plan = heldOnly ? spgpuPlanFind(handle, &key) : spgpuPlanRecord(handle, &key);
+    if (!plan || (heldOnly && plan->holds <= 0))
+        return nullptr;
+    (void)spgpuPlanLanded(plan, 0);
+    if (plan->state == SPGPU_PLAN_READY && plan->holds <= 0 && ((volatile int*)plan->pinned)[1] != 0) {
+        /* a kernel met a sub-group whose depth contradicts the plan: another matrix lives at these addresses now.  (Its
+         * results were right all the same.)  (A held plan cannot go stale: its caller has promised that the index arrays stay as they are.) */
+        h->planStales += 1;
+        plan->stales += 1;
+        const bool giveUp = planGivesUp(plan->uses, plan->stales);
+        spgpuPlanRetire(handle, plan);
+        if (giveUp)
+            plan->state = SPGPU_PLAN_GIVEN_UP;
+    }
+    if (plan->state == SPGPU_PLAN_EMPTY)
+        startPlan<IS_HELL>(handle, plan, stream);
+    return plan;
+}
+
 /*
  * The ordered SpMV of launchSlabFamily (ellpack_spmv.hip) with the matrix's plan, if it has one that is ready: true = launched,
  * nothing is to follow; false = the caller runs the path with the deep list (and, where that is possible, the analysis has been
- * started behind the scenes).  `shape`: launchRagged's (4: 2 048 rows per workgroup with staged results; otherwise 1 024
- * rows and a 64 KiB tile); tiled = false: the gather form (512 rows, no x tile).
+ * started behind the scenes).  `shape`, `tiled`: queueShape's (ordered_rules.h).
  * mustLaunch: the caller has no deep list for this stream -- without a ready plan the same kernel runs with NO plan: nothing
  * is listed, every sub-group deeper than the cap is worked off by its own block behind its stream, no x tile.  Stateless,
  * slower, the same bits.
@@ -381,114 +432,37 @@ template <typename T, bool IS_HELL>
 bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, SpmvCall call)
 {
     const bool prepareOnly = call != SpmvCall::Run;
-    constexpr int RPL = 16 / (int)sizeof(T);
-    constexpr int UNROLL = kRaggedUnroll<RPL>;
-    const SpgpuTuning* tune = spgpuTuning();
-    const bool staged = tiled && sizeof(T) <= 8 && shape == 4;
-    const int subs = !tiled ? 16 : (staged ? 64 : 32);
-    SlabArgs<T> a = in;
-    a.split = raggedSplit<T>(a.deepCap, (kWave / (32 / RPL)) * UNROLL, tune->raggedSplit);
-    a.deepHeader = nullptr;
-    a.planBlocks = nullptr;
-    a.planDeepSubs = nullptr;
-    a.planDeep = 0;
-    a.planFlags = nullptr;
-    a.planPacked = nullptr;
-    a.planDeepPerBlock = kPlanDeepMost;
-    a.planDeepStride = 0;
-    const long long subGroups = ((long long)a.rows + 31) / 32;
-    a.planMainBlocks = (int)((subGroups + subs - 1) / subs);
-    auto launch = [&]() {
-        const unsigned deepBlocks = (unsigned)((a.planDeep + kPlanDeepMost - 1) / kPlanDeepMost);
-        const unsigned grid = (unsigned)a.planMainBlocks + deepBlocks;
-        /* the workgroups of deep sub-groups spread over the first 60 % of the grid */
-        if (deepBlocks == 0u) {
-            a.planDeepStride = 0;
-        } else {
-            const unsigned long long reach = (unsigned long long)grid * 60ull / 100ull;
-            const unsigned stride = (unsigned)(reach / deepBlocks);
-            /* odd: the hardware deals workgroup ids round-robin over the 8 XCDs -- with an even stride the long-lived workgroups
-             * would pile up on one or two of them (measured: stride 8, 0.73 -> 0.94 ms, one XCD still busy 250 us after the others).
-             * In the grid: stride <= 1.5 x (reach / deepBlocks) when that is >= 1, so (deepBlocks - 1) x stride < 1.5 x reach <= 0.9 x grid. */
-            a.planDeepStride = (int)(stride < 1u ? 1u : (stride | 1u));
-        }
-#define SPGPU_PLANNED(WAVES, TILE, SUBS, ZB)                                                                          \
-    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL, WAVES, TILE, SUBS, true, ZB, true>), dim3(grid), dim3((WAVES) * kWave), 0, stream, a)
-        if (!tiled) {
-            SPGPU_PLANNED(4, 0, 16, 0);
-        } else if constexpr (sizeof(T) <= 8) {
-#define SPGPU_PLANNED_PACKED(WAVES, TILE, SUBS, ZB)                                                                   \
-    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL + kPackedMoreUnroll, WAVES, TILE, SUBS, true, ZB, true, true>), dim3(grid), dim3((WAVES) * kWave), 0, stream, a)
-            if (a.planPacked) { /* a frozen matrix: 16-bit indices */
-                if (staged)
-                    SPGPU_PLANNED_PACKED(8, 49152, 64, 17408);
-                else
-                    SPGPU_PLANNED_PACKED(8, 65536, 32, 0);
-            } else if (staged)
-                SPGPU_PLANNED(8, 49152, 64, 17408);
-            else
-                SPGPU_PLANNED(8, 65536, 32, 0);
-        } else {
-            SPGPU_PLANNED(8, 65536, 32, 0);
-        }
-#undef SPGPU_PLANNED
-#undef SPGPU_PLANNED_PACKED
-    };
-
+    const bool staged = stagedShape(sizeof(T), tiled, shape);
+    const int subs = planSubs(sizeof(T), tiled, shape);
+    SlabArgs<T> a = unplannedArgs(in, subs);
     /* a captured launch carries the plan's addresses for as long as the graph lives, and plans are retired: in a capture only a
      * HELD plan (spgpuSpmvHold, include/spgpu/ext/graph.h), which the host never retires, is used -- looked up, never made */
     const bool heldOnly = spgpuStreamCapturing(stream);
     bool launched = false;
-    if (tune->plan && in.rIdx && (!heldOnly || !prepareOnly)) {
-        const SpgpuSpmvPlan key = planKey(in, in.rIdx, in.deepCap, subs);
+    if (spgpuTuning()->plan && in.rIdx && (!heldOnly || !prepareOnly)) {
         SpgpuPrivateHandle* h = spgpuPrivate(handle);
         spgpuTablesLock(handle);
-        SpgpuSpmvPlan* plan = heldOnly ? spgpuPlanFind(handle, &key) : spgpuPlanRecord(handle, &key);
-        if (plan && heldOnly && plan->holds <= 0)
-            plan = nullptr;
-        if (plan) {
-            (void)spgpuPlanLanded(plan, 0);
-            if (plan->state == SPGPU_PLAN_READY && plan->holds <= 0 && ((volatile int*)plan->pinned)[1] != 0) {
-                /* a kernel met a sub-group whose depth contradicts the plan: another matrix lives at these addresses now.  (Its
-                 * results were right all the same.)  A matrix that keeps changing under a young plan is left alone after the third time.
-                 * (A held plan cannot go stale: its caller has promised that the index arrays stay as they are.) */
-                h->planStales += 1;
-                plan->stales += 1;
-                const bool giveUp = plan->uses < 16 && plan->stales >= 3;
-                spgpuPlanRetire(handle, plan);
-                if (giveUp)
-                    plan->state = SPGPU_PLAN_GIVEN_UP;
+        SpgpuSpmvPlan* plan = currentPlan<IS_HELL>(handle, stream, planKey(in, in.rIdx, in.deepCap, subs), heldOnly);
+        if (plan && prepareOnly) {
+            launched = spgpuPlanLanded(plan, 1) != 0;
+            if (call == SpmvCall::Freeze) { /* freeze: true = the plan has its 16-bit indices */
+                if (launched && !plan->packed && mayPack(tiled, sizeof(T), subs))
+                    (void)packPlan<IS_HELL>(plan, handle, stream);
+                launched = launched && plan->packed != nullptr;
+                if (launched)
+                    h->planFreezes += 1;
             }
-            if (plan->state == SPGPU_PLAN_EMPTY)
-                startPlan<IS_HELL>(handle, plan, stream);
-            if (prepareOnly) {
-                launched = spgpuPlanLanded(plan, 1) != 0;
-                if (call == SpmvCall::Freeze) { /* freeze: true = the plan has its 16-bit indices */
-                    if (launched && !plan->packed && tiled && sizeof(T) <= 8 && (subs == 64 || subs == 32))
-                        (void)packPlan<IS_HELL>(plan, handle, stream);
-                    launched = launched && plan->packed != nullptr;
-                    if (launched)
-                        h->planFreezes += 1;
-                }
-            } else if (plan->state == SPGPU_PLAN_READY) {
-                const size_t blockBytes = roundUp16((size_t)plan->blocks * sizeof(SpgpuPlanBlock)), countBytes = roundUp16((size_t)plan->blocks * sizeof(int));
-                a.planBlocks = static_cast<const SpgpuPlanBlock*>(plan->device);
-                a.planDeepSubs = reinterpret_cast<const int*>(static_cast<const char*>(plan->device) + blockBytes + countBytes);
-                a.planDeep = plan->deep;
-                a.planMainBlocks = plan->blocks;
-                a.planFlags = plan->pinned;
-                if (tiled && sizeof(T) <= 8)
-                    a.planPacked = static_cast<const unsigned short*>(plan->packed);
-                launch(); /* (under the lock: a retirement on another host thread waits for this launch to be queued) */
-                plan->uses += 1;
-                h->planUses += 1;
-                launched = true;
-            }
+        } else if (plan && plan->state == SPGPU_PLAN_READY) {
+            attachPlan(a, plan, tiled);
+            launchWithPlan<T, IS_HELL>(stream, a, tiled, staged); /* (under the lock: a retirement on another host thread waits for this launch to be queued) */
+            plan->uses += 1;
+            h->planUses += 1;
+            launched = true;
         }
         spgpuTablesUnlock(handle);
     }
     if (!launched && mustLaunch && !prepareOnly) {
-        launch();
+        launchWithPlan<T, IS_HELL>(stream, a, tiled, staged);
         launched = true;
     }
     return launched;

@@ -51,9 +51,8 @@ template <int M, typename T> __device__ inline T partnerOf(T v)
     return out;
 }
 
-/* Most chunks a split sub-group may have (see SPLIT below): what the tightest tiled shape -- 48 KiB of LDS behind 2 048 rows --
- * can park when every one of its sub-groups is split.  fp64 / complex fp32: 3, fp32: 6, complex fp64: 1 (never split). */
-template <typename T> constexpr int kRaggedMostChunks = 49152 / (int)sizeof(T) / 2048;
+/* Most chunks a split sub-group may have (see SPLIT below; ordered_rules.h) */
+template <typename T> constexpr int kRaggedMostChunks = raggedMostChunks(sizeof(T));
 
 #include "deep_rows.hip.h"
 
@@ -716,49 +715,27 @@ void raggedSpmvKernel(const SlabArgs<T> a) /* 4 wavefronts per SIMD: two 8-wavef
 #endif
 }
 
-/* wave-wide loads per stage; 3 keeps the 8-byte kernels at 112 VGPRs (4 wavefronts per SIMD: two 8-wavefront workgroups per CU) with two stages in flight */
-template <int RPL> constexpr int kRaggedUnroll = RPL >= 4 ? 2 : 3;
-/* Shapes (SPGPU_RAGGED_SHAPE; 0 is the default, 4 the staged one): workgroup lanes / tile / sub-groups per workgroup. */
-/* Returns true if the deep kernels have to follow (false: the launch runs the deep list's items itself). */
-/* Columns per chunk of a split sub-group (raggedSpmvKernel, SPLIT): about 96 (8 stages of the 8-byte kernels), and large
- * enough that the chunk sums of a workgroup whose sub-groups are ALL deepCap deep -- the hacks of set-aside long rows -- fit
- * behind the x tile, which is of no use to such a workgroup anyway.  The SAME value for every shape and form (the sums must not
- * depend on which of them AUTO takes): tests/oracle_api.py ragged_split restates this. */
-template <typename T> static int raggedSplit(int deepCap, int step, int asked)
+/* ---- host: which shape runs, over which grid and with which split is decided in ordered_rules.h ---------------------------------- */
+template <int RPL> constexpr int kRaggedUnroll = raggedUnroll(RPL);
+
+/* The one launch of raggedSpmvKernel: a shape (queueShape), field by field, as the kernel's own template parameter list.  STAGED names
+ * the staged shape where the type has it (complex fp64: the tiled one again, the same instantiation). */
+template <typename T, bool IS_HELL, bool TILED, bool STAGED, bool PLAN, bool PACKED>
+static void launchQueue(hipStream_t stream, unsigned grid, const SlabArgs<T>& a)
 {
-    constexpr int most = kRaggedMostChunks<T>;
-    if (most < 2 || deepCap <= 0 || asked == 0)
-        return 0;
-    const int want = ((asked > 0 ? asked : 96) + step - 1) / step * step;
-    const int need = ((deepCap + most - 1) / most + step - 1) / step * step;
-    return want > need ? want : need;
+    constexpr QueueShape s = queueShape(sizeof(T), TILED, STAGED ? kStagedShape : 0);
+    constexpr int RPL = wideOf(sizeof(T));
+    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, kRaggedUnroll<RPL>, s.waves, s.tileBytes, s.subs, true, s.zBytes, PLAN, PACKED>), dim3(grid),
+                       dim3(s.waves * kWave), 0, stream, a);
 }
 
-template <typename T, int RPL, bool IS_HELL, bool DEEP>
-static bool launchRagged(hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled)
+/* Without a plan: the sub-groups deeper than deepCap register in the stream's deep list (the deep kernels follow: launchOrdered). */
+template <typename T, bool IS_HELL>
+static void launchRagged(hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled)
 {
-    constexpr int UNROLL = kRaggedUnroll<RPL>;
     SlabArgs<T> a = in;
-    a.split = raggedSplit<T>(a.deepCap, (kWave / (32 / RPL)) * UNROLL, spgpuTuning()->raggedSplit);
-    const long long subs = ((long long)a.rows + 31) / 32;
-#define LAUNCH_RAGGED(WAVES, TILE, SUBS)                                                                              \
-    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL, WAVES, TILE, SUBS, DEEP>),                          \
-                       dim3((unsigned)((subs + (SUBS) - 1) / (SUBS))), dim3((WAVES) * kWave), 0, stream, a)
-#define LAUNCH_RAGGED_Z(WAVES, TILE, SUBS, ZB)                                                                        \
-    hipLaunchKernelGGL((raggedSpmvKernel<T, RPL, IS_HELL, UNROLL, WAVES, TILE, SUBS, DEEP, ZB>),                      \
-                       dim3((unsigned)((subs + (SUBS) - 1) / (SUBS))), dim3((WAVES) * kWave), 0, stream, a)
-    if (!tiled) {
-        LAUNCH_RAGGED(4, 0, 16);
-        return true;
-    }
-    if constexpr (sizeof(T) <= 8) { /* (16-byte elements: tile + staging leave room for one workgroup per CU -- the default shape) */
-        if (shape == 4) { /* 2 048 rows per workgroup, results staged by destination */
-            LAUNCH_RAGGED_Z(8, 49152, 64, 17408);
-            return true;
-        }
-    }
-    LAUNCH_RAGGED(8, 65536, 32);
-    return true;
-#undef LAUNCH_RAGGED
-#undef LAUNCH_RAGGED_Z
+    a.split = raggedSplit(sizeof(T), a.deepCap, spgpuTuning()->raggedSplit);
+    const unsigned grid = queueGrid(a.rows, queueShape(sizeof(T), tiled, shape).subs);
+    withConstants([&](auto gather, auto staged) { launchQueue<T, IS_HELL, !gather, staged, false, false>(stream, grid, a); }, !tiled,
+                  stagedShape(sizeof(T), tiled, shape));
 }

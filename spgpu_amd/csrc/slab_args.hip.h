@@ -1,12 +1,12 @@
 #pragma once
 /*
  * What the ELL / HELL SpMV kernels are handed (one struct for every kernel of the family), and the pieces more than one
- * translation unit of the family needs: ellpack_spmv.hip (the dispatch; the kernels for rows as they come, the queue kernel for ordered
+ * translation unit of the family needs (the ordered path's launch rules among them: ordered_rules.h): ellpack_spmv.hip (the dispatch; the kernels for rows as they come, the queue kernel for ordered
  * rows with its deep list) and planned_spmv.hip (the queue kernel driven by a per-matrix plan).
  */
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
-#include "spmv_rules.h" /* kBlockThreads, kTailLanes, kTailUnroll */
+#include "ordered_rules.h" /* the ordered path's launch rules; spmv_rules.h: kBlockThreads, kTailLanes, kTailUnroll */
 
 namespace spgpu {
 
@@ -42,7 +42,7 @@ template <typename T> struct SlabArgs {
     T* deepItemSums;             /* [SPGPU_DEEP_ITEMS][32] */
     int* deepOverflow;           /* pinned: calls that overflowed the list, and what the last of them asked for */
     int avgNnzPerRow;            /* the caller's hint (0: none) */
-    int split;                   /* raggedSpmvKernel: columns per chunk of a split sub-group (0: none) */
+    int split;                   /* raggedSpmvKernel: columns per chunk of a split sub-group (0: none; ordered_rules.h: raggedSplit) */
     /* raggedSpmvKernel<..., PLAN> (planned_spmv.hip): the matrix's plan (spgpu_internal.h) */
     const SpgpuPlanBlock* planBlocks; /* [planMainBlocks] */
     const int* planDeepSubs;          /* [planDeep] sub-groups that get workgroups of their own, ascending */
@@ -50,7 +50,7 @@ template <typename T> struct SlabArgs {
     int planMainBlocks;               /* workgroups that own blocks of rows; the rest of the grid owns deep sub-groups */
     int planDeepPerBlock;             /* deep sub-groups per such workgroup: always kPlanDeepMost (as a constant it moves 4 bytes of
                                        * scratch into the complex fp64 tiled kernel) */
-    int planDeepStride;               /* such a workgroup at every planDeepStride-th place of the grid, from the front (0: all of them at the end) */
+    int planDeepStride;               /* such a workgroup at every planDeepStride-th place of the grid, from the front (0: all of them at the end; ordered_rules.h: planDeepStride) */
     int* planFlags;                   /* pinned; [1] = 1: a kernel found the plan contradicting the matrix */
     const int* packBases;             /* slabSpmvKernel<..., PACKED> (a frozen matrix without a row order): the column the 16-bit words of
                                        * every group of rows (one wavefront's) count from */
@@ -109,7 +109,8 @@ template <typename T> inline SpgpuSpmvPlan planKey(const SlabArgs<T>& a, const i
  * would leave to later calls are made now and waited for.  Freeze (spgpu?SpmvFreeze): the same, plus the 16-bit copy of the indices. */
 enum class SpmvCall { Run, Prepare, Freeze };
 
-/* planned_spmv.hip: the ordered SpMV with the matrix's plan, if it has one that is ready (true: launched, nothing follows) */
+/* planned_spmv.hip: the ordered SpMV with the matrix's plan, if it has one that is ready (true: launched, nothing follows); shape, tiled:
+ * queueShape's (ordered_rules.h) */
 template <typename T, bool IS_HELL> bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& in, int shape, bool tiled, bool mustLaunch, SpmvCall call);
 
 constexpr int kDeepChunk = 64; /* columns per deep item; measured: items of 32 / 64 / 128 columns and stages of 16 / 32 within 8 % -- the kernel is bound by the lines its gathers pull */

@@ -111,6 +111,9 @@ typedef struct SpgpuDeepList {
     void* itemSums;          /* [SPGPU_DEEP_ITEMS][32] x 16 bytes */
     hipEvent_t idle;         /* to be recorded behind the kernels that use the list */
 } SpgpuDeepList;
+/* Device memory on the handle's device -- where its streams run, whatever device the caller has current (and keeps).  NULL: no memory
+ * (the error is taken back). */
+void* spgpuDeviceAlloc(spgpuHandle_t h, size_t bytes);
 /* Device pointers of the current stream's list, or SPGPU_UNSUPPORTED when that stream has none. */
 spgpuStatus_t spgpuDeepScratch(spgpuHandle_t h, SpgpuDeepList* list);
 /* The current stream's list has gone into a captured graph: it stays with that stream for the handle's lifetime. */
@@ -123,7 +126,8 @@ void spgpuDeepListPin(spgpuHandle_t h);
  * are too deep for a block (registered through atomics in a list, worked off by two launches BEHIND the main kernel).  An
  * analysis pass -- started by the first SpMV that sees the matrix, on its stream, not waited for -- writes both down once:
  * a 32-byte record per block of SUBS sub-groups, and the list of deep sub-groups, which then get workgroups of their own in the
- * SAME launch.  Later calls on the same arrays find the plan by its key.
+ * SAME launch.  Later calls on the same arrays find the plan by its key.  Which kernel shape a plan is made for, its grid, its buffer's
+ * layout, when it is given up and when it may get a 16-bit index copy: csrc/ordered_rules.h.
  *
  * A plan decides only WHO computes a sub-group and WHERE the LDS tile lies -- never what is read or in which order it is
  * added: every kernel reads the row lengths, slab bases and destinations of the matrix as it is at the call and derives the
@@ -143,7 +147,7 @@ typedef struct SpgpuSpmvPlan {
     /* key: the arrays the analysis read, and what it assumed */
     const void *rP, *rS, *rIdx, *hackOffsets;
     long long idxStride;
-    int rows, hackSize, baseIndex, maxNnz, deepCap, subs; /* subs: 32-row sub-groups per block; < 0: the frozen record of a matrix WITHOUT a
+    int rows, hackSize, baseIndex, maxNnz, deepCap, subs; /* subs: 32-row sub-groups per block (ordered_rules.h: planSubs); < 0: the frozen record of a matrix WITHOUT a
                                                            * row order (frozen_slab.hip.h freezeSlab): -rows per group, `device` = the groups' bases */
     /* state */
     int state;      /* SPGPU_PLAN_EMPTY ... */
@@ -152,7 +156,7 @@ typedef struct SpgpuSpmvPlan {
     unsigned clock; /* last looked up (least recently used goes first) */
     int blocks;     /* blocks of `subs` sub-groups */
     int deep;       /* deep sub-groups (read from pinned[0] once the analysis has completed) */
-    void* device;   /* one allocation: SpgpuPlanBlock[blocks] | int counts[blocks] | int deepSubs[sub-groups] */
+    void* device;   /* one allocation: SpgpuPlanBlock[blocks] | int counts[blocks] | int deepSubs[sub-groups] (ordered_rules.h: planLayout) */
     long long packedBytes;
     void* packed;   /* frozen matrices only (spgpu?SpmvFreeze, include/spgpu/tuning.h), else NULL: the column indices of the rows the blocks walk
                      * themselves as 16-bit offsets from the block's packBase, slot for slot as in rP (0xFFFF: ask rP) */

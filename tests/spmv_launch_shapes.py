@@ -47,18 +47,23 @@ AUTO, GATHER, STRIPS, XTILE, SWEEP = range(5)
 FORM_NAME = {AUTO: "auto", GATHER: "gather", STRIPS: "strips", XTILE: "xtile", SWEEP: "sweep"}
 
 
-_PROGRAM = []
+_PROGRAMS = {}
+
+
+def rules_program(directory, name):
+    """tests/<name>.cpp, a stand-alone program around one of the rule headers of spgpu_amd/csrc, built into `directory` with the
+    undefined-behaviour sanitizer (once per process): the path of the executable."""
+    if name not in _PROGRAMS:
+        exe = os.path.join(str(directory), name)
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
+                        os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], check=True)
+        _PROGRAMS[name] = exe
+    return _PROGRAMS[name]
 
 
 def dispatch_program(directory):
-    """tests/spmv_dispatch_cases.cpp, the stand-alone program around spgpu_amd/csrc/spmv_rules.h, built into `directory` with the
-    undefined-behaviour sanitizer (once per process): the path of the executable."""
-    if not _PROGRAM:
-        exe = os.path.join(str(directory), "spmv_dispatch_cases")
-        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                        os.path.join(ROOT, "tests", "spmv_dispatch_cases.cpp"), "-o", exe], check=True)
-        _PROGRAM.append(exe)
-    return _PROGRAM[0]
+    """tests/spmv_dispatch_cases.cpp, the program around spgpu_amd/csrc/spmv_rules.h."""
+    return rules_program(directory, "spmv_dispatch_cases")
 
 
 def header_constants(program):
