@@ -21,6 +21,7 @@
  * A reduction is two kernels (block partials; one wavefront that combines them: 16 per lane, then a lane-xor tree).
  * The same calls for the vectors of a pitch multivector, one result / coefficient per vector: spgpu/ext/device_scalars_mv.h.
  * The Jacobi step of preconditioned CG fused into these calls, and a matrix' diagonal: spgpu/ext/precond.h.
+ * The fused SpMV + dot below for matrices kept in HDIA or DIA: spgpu/ext/hdia_solver.h.
  * tools/cg_amd.c runs CG both ways (eager with host scalars, and one captured
  * graph per iteration with these) and compares the iterates.
  */

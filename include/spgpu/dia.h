@@ -11,6 +11,7 @@
  * handle->currentStream.  On MI355X this is the HDIA kernel run over one
  * all-rows hack (the addressing is identical with hackSize = dMPitch).
  * Several vectors at once (vector j at base + j*pitch): spgpu?diaspmmMv, spgpu/ext/hdia_spmm.h.
+ * Fused with the dot w . z of a captured CG iteration: spgpu?diaspmvDotDevice, spgpu/ext/hdia_solver.h.
  */
 #include "core.h"
 

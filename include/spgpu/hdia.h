@@ -14,6 +14,7 @@
  *   A stored slot contributes iff 0 <= offsets[d] + r < cols.
  * z may alias y exactly.  Calls are asynchronous on handle->currentStream.
  * Several vectors at once (vector j at base + j*pitch): spgpu?hdiaspmmMv, spgpu/ext/hdia_spmm.h.
+ * Fused with the dot w . z of a captured CG iteration: spgpu?hdiaspmvDotDevice, spgpu/ext/hdia_solver.h.
  */
 #include "core.h"
 

@@ -311,6 +311,16 @@ for _L in "SD":
     maxpby_pair_axy_dot_device[_L] = _decl(f"spgpu{_L}maxpbyPairAxyDotDevice", None,
                                            [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
 
+# ---- ext/hdia_solver.h: the fused SpMV + dot of a captured CG iteration on HDIA / DIA: result, w, then spgpu?hdiaspmv's /
+# spgpu?diaspmv's arguments ----------
+hdiaspmv_dot_device, diaspmv_dot_device = {}, {}
+for _L in "SD":
+    _S = SCALAR[_L]
+    hdiaspmv_dot_device[_L] = _decl(f"spgpu{_L}hdiaspmvDotDevice", None,
+                                    [Handle, ptr, ptr, ptr, ptr, _S, ptr, ptr, i32, ptr, i32, i32, ptr, _S])
+    diaspmv_dot_device[_L] = _decl(f"spgpu{_L}diaspmvDotDevice", None,
+                                   [Handle, ptr, ptr, ptr, ptr, _S, ptr, ptr, i32, i32, i32, i32, ptr, _S])
+
 # ---- tuning.h: per-handle kernel-form hint ---------------------------------------------------------------------
 FORM_AUTO, FORM_GATHER, FORM_STRIPS, FORM_XTILE, FORM_SWEEP = range(5)
 spgpuSetSpmvForm = _decl("spgpuSetSpmvForm", None, [Handle, i32])

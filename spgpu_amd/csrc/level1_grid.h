@@ -1,6 +1,6 @@
 #pragma once
 /*
- * Where the Level-1 calls (level1.hip) and the fused solver steps (fused_solver.hip) choose their launches.  Plain host C++17, no
+ * Where the Level-1 calls (level1.hip) and the fused solver steps (fused_solver.hip, fused_hdia.hip) choose their launches.  Plain host C++17, no
  * HIP header: the rules compile and run on their own (tests/level1_grid_cases.cpp).
  *
  * Every kernel of the family has one shape: kL1Threads lanes, kL1Unroll accesses in flight per lane -- of 16 bytes (WIDE elements)
@@ -15,6 +15,8 @@
  *                                     passes of `cap` vectors cap / vectors of the pass      wide only
  *   dotDevice, nrm2Device, axpbyPairDot, hellspmvDot (reduceGrid, one vector)
  *                                     one launch              cap                            never (spgpu?dot does: see DESIGN.md 3.9)
+ *   hdiaspmvDot, diaspmvDot (fused_hdia.hip; reduceGrid, one vector: on w and z, as hellspmvDot; packedStrips for the coefficients)
+ *                                     one launch              cap                            never (no such kernel)
  *   maxpbyPairDot (reduceGrid)        passes of `cap` vectors cap / vectors of the pass      never (no such kernel)
  *   axyDot, axpbyPairAxyDot (reduceGrid, one vector: on r and z, resp. on z2 as axpbyPairDot; d and w never count)
  *                                     one launch              cap                            never (no such kernel)
@@ -129,6 +131,13 @@ inline bool packedRows(size_t elemBytes, bool wide, int hackSize, const void* cM
 {
     const int rows = wideOf(elemBytes);
     return wide && hackSize % rows == 0 && allAligned(16, {cM}) && allAligned(4 * rows, {rP, rS});
+}
+
+/* hdiaspmvDot, diaspmvDot: the VEC consecutive rows of a pack lie in one hack (DIA: one pitch) and their coefficients on a diagonal
+ * are one 16-byte load. */
+inline bool packedStrips(size_t elemBytes, bool wide, int hackSizeOrPitch, const void* dM)
+{
+    return wide && hackSizeOrPitch % wideOf(elemBytes) == 0 && allAligned(16, {dM});
 }
 
 /* Run-time choices as compile-time constants: f(std::bool_constant of each choice, in order).  A kernel's argument list is then
