@@ -22,6 +22,7 @@
  * A holder of CSR needs none of this: ext/csr_device.h builds the same ELL and HELL arrays from csrRowPtr / csrColIndices /
  * csrValues with no sort and no scratch (spgpuCsrRowLengthsDevice, spgpuCsrToEllDevice, spgpuCsrToHellDevice), and takes its
  * hackOffsets from spgpuHellPlanDevice below, for which `work` of spgpuCooConvertWorkBytes(rowsCount, 0) bytes is enough.
+ * The transpose of a stored HELL or ELL matrix is built the same way, as a HELL matrix, by ext/transpose_device.h.
  */
 #include "core.h"
 

@@ -214,6 +214,24 @@ CSR_FILL_CHUNK = _bind("spgpuCsrFillChunk", i32, [])()
 CSR_FILL_DEFAULT = _bind("spgpuCsrDefaultFill", i32, [])()
 
 
+# ---- ext/transpose_device.h: the HELL arrays of A^T from a stored HELL or ELL matrix, in HBM -------------------------------
+spgpuHellTransposeWorkBytes = _decl("spgpuHellTransposeWorkBytes", C.c_size_t, [i32, i32, i32])
+# (handle, tLengths, &maxRowSize, &nonZeros, rP, hackSize, hackOffsets, rS, rIdx, rows, cols, baseIndex, slots, work)
+spgpuHellTransposeLengthsDevice = _decl("spgpuHellTransposeLengthsDevice", i32,
+                                        [Handle, ptr, C.POINTER(i32), C.POINTER(i32), ptr, i32, ptr, ptr, ptr, i32, i32, i32, i32, ptr])
+# (handle, tValues, tIndices, tHackOffsets, tHackSize, tBaseIndex, cM, rP, hackSize, hackOffsets, rS, rIdx, rows, cols, baseIndex,
+#  slots, valuesType, tLengths, work)
+spgpuHellTransposeDevice = _decl("spgpuHellTransposeDevice", i32,
+                                 [Handle, ptr, ptr, ptr, i32, i32, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr])
+# (handle, tLengths, &maxRowSize, &nonZeros, rP, ellIndicesPitch, rS, rIdx, rows, cols, baseIndex, slots, work)
+spgpuEllTransposeLengthsDevice = _decl("spgpuEllTransposeLengthsDevice", i32,
+                                       [Handle, ptr, C.POINTER(i32), C.POINTER(i32), ptr, i32, ptr, ptr, i32, i32, i32, i32, ptr])
+# (handle, tValues, tIndices, tHackOffsets, tHackSize, tBaseIndex, cM, rP, ellValuesPitch, ellIndicesPitch, rS, rIdx, rows, cols,
+#  baseIndex, slots, valuesType, tLengths, work)
+spgpuEllTransposeDevice = _decl("spgpuEllTransposeDevice", i32,
+                                [Handle, ptr, ptr, ptr, i32, i32, ptr, ptr, i32, i32, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr])
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -13,6 +13,7 @@
  * atomics anywhere (round 1 bucketed with an atomic cursor and recovered k by counting smaller ids in the bucket --
  * quadratic in the row length, minutes for a row of 10^5 entries).
  */
+#include "convert_scan.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -24,10 +25,6 @@
 
 namespace spgpu {
 
-constexpr int kCvThreads = 256;
-constexpr int kScanPerThread = 4;
-constexpr int kScanTile = kCvThreads * kScanPerThread;
-
 struct ConvertWork {
     int* rowStart;
     int* cursor; /* per-hack depths of the HELL plan */
@@ -37,9 +34,6 @@ struct ConvertWork {
     int* bucket; /* entry ids sorted by row */
     void* temp;
 };
-
-static size_t scanBlocks(long long n) { return (size_t)((n + kScanTile - 1) / kScanTile); }
-static size_t alignUpCv(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* zero-based row of a COO entry as the sort key; anything outside the matrix becomes `rows` */
 struct RowKeyOf {
@@ -61,8 +55,6 @@ static hipError_t sortTempBytes(size_t nnz, size_t* bytes)
     return err;
 }
 
-static size_t fixedInts(int rows) { return alignUpCv((size_t)16 + 2 * (size_t)rows + 1 + scanBlocks((long long)rows + 1) + 2, 64); }
-
 static ConvertWork carve(void* work, int rows, int nnz)
 {
     ConvertWork w;
@@ -81,136 +73,6 @@ static ConvertWork carve(void* work, int rows, int nnz)
     p += alignUpCv((size_t)(nnz > 0 ? nnz : 0), 64);
     w.temp = p;
     return w;
-}
-
-static unsigned gridFor(long long n)
-{
-    const long long blocks = (n + kCvThreads - 1) / kCvThreads;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > 1048576 ? 1048576 : blocks));
-}
-
-/* rowStart[r] = first sorted position whose row is >= r, r = 0 .. rows */
-__global__ __launch_bounds__(kCvThreads) void rowStartKernel(int* rowStart, int rows, const unsigned* rowOf, int nnz)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long r = (long long)blockIdx.x * kCvThreads + threadIdx.x; r <= rows; r += stride) {
-        int lo = 0, hi = nnz;
-        while (lo < hi) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (rowOf[mid] < (unsigned)r)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        rowStart[r] = lo;
-    }
-}
-
-__global__ __launch_bounds__(kCvThreads) void rowLengthsKernel(int* rowLengths, const int* rowStart, int rows, int nnz, int* misc)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long r = (long long)blockIdx.x * kCvThreads + threadIdx.x; r < rows; r += stride)
-        rowLengths[r] = rowStart[r + 1] - rowStart[r];
-    if (blockIdx.x == 0 && threadIdx.x == 0 && rowStart[rows] < nnz)
-        misc[1] = 1; /* entries outside the matrix: reported to the host, the entries skipped */
-}
-
-__global__ __launch_bounds__(kCvThreads) void maxKernel(const int* values, long long n, int scale, int* misc)
-{
-    int best = 0;
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long i = (long long)blockIdx.x * kCvThreads + threadIdx.x; i < n; i += stride)
-        best = values[i] > best ? values[i] : best;
-    best = waveMax(best);
-    if ((threadIdx.x & (kWave - 1)) == 0 && best > 0)
-        atomicMax(&misc[0], best * scale);
-}
-
-/* ---- exclusive scan in three launches: tile scans, scan of the tile totals, add-back ---- */
-__device__ inline int blockExclusiveScan(int value, int* ldsWaveTotals, int* blockTotal)
-{
-    /* inclusive scan inside the wavefront with lane shuffles */
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    int incl = value;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int up = __shfl_up(incl, d, kWave);
-        if (lane >= d)
-            incl += up;
-    }
-    if (lane == kWave - 1)
-        ldsWaveTotals[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kCvThreads / kWave; ++w) {
-        if (w < wave)
-            before += ldsWaveTotals[w];
-        total += ldsWaveTotals[w];
-    }
-    __syncthreads();
-    *blockTotal = total;
-    return before + incl - value;
-}
-
-/* out[i] = sum_{j<i} in[j]*scale within the tile; tile total to totals[tile].  in == NULL scans totals in place. */
-__global__ __launch_bounds__(kCvThreads) void scanTilesKernel(int* out, const int* in, long long n, int scale, int* totals)
-{
-    __shared__ int waveTotals[kCvThreads / kWave];
-    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanPerThread;
-    int v[kScanPerThread], mine = 0;
-#pragma unroll
-    for (int j = 0; j < kScanPerThread; ++j) {
-        v[j] = base + j < n ? in[base + j] * scale : 0;
-        mine += v[j];
-    }
-    int total;
-    int run = blockExclusiveScan(mine, waveTotals, &total);
-#pragma unroll
-    for (int j = 0; j < kScanPerThread; ++j) {
-        if (base + j < n)
-            out[base + j] = run;
-        run += v[j];
-    }
-    if (threadIdx.x == 0)
-        totals[blockIdx.x] = total;
-}
-
-/* single workgroup: exclusive scan of `count` tile totals in place, grand total to totals[count] */
-__global__ __launch_bounds__(kCvThreads) void scanTotalsKernel(int* totals, long long count)
-{
-    __shared__ int waveTotals[kCvThreads / kWave];
-    int carry = 0;
-    for (long long first = 0; first < count; first += kCvThreads) {
-        const long long i = first + threadIdx.x;
-        const int v = i < count ? totals[i] : 0;
-        int total;
-        const int excl = blockExclusiveScan(v, waveTotals, &total);
-        if (i < count)
-            totals[i] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0)
-        totals[count] = carry;
-}
-
-__global__ __launch_bounds__(kCvThreads) void addTotalsKernel(int* out, long long n, const int* totals)
-{
-    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanPerThread;
-    const int add = totals[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < kScanPerThread; ++j)
-        if (base + j < n)
-            out[base + j] += add;
-}
-
-/* out[0..n) = exclusive scan of in[0..n)*scale; the grand total lands in totals[tiles] (device). */
-static void exclusiveScan(hipStream_t s, int* out, const int* in, long long n, int scale, int* totals)
-{
-    const size_t tiles = scanBlocks(n);
-    hipLaunchKernelGGL(scanTilesKernel, dim3((unsigned)tiles), dim3(kCvThreads), 0, s, out, in, n, scale, totals);
-    hipLaunchKernelGGL(scanTotalsKernel, dim3(1), dim3(kCvThreads), 0, s, totals, (long long)tiles);
-    hipLaunchKernelGGL(addTotalsKernel, dim3((unsigned)tiles), dim3(kCvThreads), 0, s, out, n, totals);
 }
 
 /* Longest row of every hack (hell.c:71-88). */
@@ -377,8 +239,8 @@ spgpuStatus_t spgpuCooRowLengthsDevice(spgpuHandle_t handle, int* rowLengths, in
                                       rocprim::counting_iterator<int>(0), w.bucket, (size_t)nonZerosCount, 0, bits, s) != hipSuccess)
             return SPGPU_UNSPECIFIED;
     }
-    hipLaunchKernelGGL(rowStartKernel, dim3(gridFor((long long)rowsCount + 1)), dim3(kCvThreads), 0, s, w.rowStart, rowsCount,
-                       (const unsigned*)w.rowOf, nonZerosCount > 0 ? nonZerosCount : 0);
+    hipLaunchKernelGGL(rowStartKernel<unsigned>, dim3(gridFor((long long)rowsCount + 1)), dim3(kCvThreads), 0, s, w.rowStart, rowsCount,
+                       (const unsigned*)w.rowOf, 0, nonZerosCount > 0 ? nonZerosCount : 0);
     hipLaunchKernelGGL(rowLengthsKernel, dim3(gridFor(rowsCount)), dim3(kCvThreads), 0, s, rowLengths, (const int*)w.rowStart,
                        rowsCount, nonZerosCount > 0 ? nonZerosCount : 0, w.misc);
     hipLaunchKernelGGL(maxKernel, dim3(gridFor(rowsCount)), dim3(kCvThreads), 0, s, rowLengths, (long long)rowsCount, 1, w.misc);

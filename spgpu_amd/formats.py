@@ -145,6 +145,75 @@ def oell_order(row_lengths, window=0, long_rows=0, aligned=False):
     return r_idx[:n], dst[:n]
 
 
+def _transposed_coo(indices, values, row_lengths, first, step, value_first, value_step, r_idx, base):
+    lengths = np.asarray(row_lengths, np.int64)
+    n, total = int(lengths.size), int(lengths.sum())
+    r = np.repeat(np.arange(n, dtype=np.int64), lengths)
+    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(lengths) - lengths, lengths)
+    i = r if r_idx is None else np.asarray(r_idx, np.int64)[r]
+    j = np.asarray(indices)[first[r] + k * step].astype(np.int64) - base
+    order = np.argsort(i, kind="stable")              # ascending matrix row; the slots of a row keep their order
+    order = order[np.argsort(j[order], kind="stable")]  # then by column: entry k of row j of A^T = k-th entry of column j of A
+    taken = np.asarray(values)[(value_first[r] + k * value_step)[order]]
+    return j[order].astype(np.int32), i[order].astype(np.int32), np.ascontiguousarray(taken)
+
+
+def hell_transposed_coo(hell, r_idx=None):
+    """The COO listing of A^T in the order include/spgpu/ext/transpose_device.h defines, from host HELL arrays (a dict of
+    ell_to_hell): zero-based (rows of A^T = columns of A, columns of A^T = matrix rows i of A, values), the entries of A taken
+    by ascending i = r_idx[r] (r without r_idx) and within a row by ascending slot.  Padding slots are never looked at."""
+    hs = hell["hack_size"]
+    r = np.arange(hell["rows"], dtype=np.int64)
+    first = np.asarray(hell["hack_offsets"], np.int64)[r // hs] + r % hs if r.size else r
+    return _transposed_coo(hell["indices"], hell["values"], hell["row_lengths"][:hell["rows"]], first, hs, first, hs, r_idx, hell["base"])
+
+
+def ell_transposed_coo(ell, r_idx=None, values_pitch=None):
+    """hell_transposed_coo for host ELL arrays (a dict of coo_to_ell; values_pitch if it differs from the indices' pitch)."""
+    r = np.arange(ell["rows"], dtype=np.int64)
+    return _transposed_coo(ell["indices"], ell["values"], ell["row_lengths"][:ell["rows"]], r, ell["pitch"], r,
+                           values_pitch or ell["pitch"], r_idx, ell["base"])
+
+
+def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
+                          t_base=0, ell_pitches=None):
+    """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
+    the C ABI: spgpu{Hell,Ell}TransposeLengthsDevice -> spgpuHellPlanDevice -> spgpu{Hell,Ell}TransposeDevice.
+    Returns a dict of torch tensors (cM, rP, hack_offsets, rS) plus sizes; rows = n_cols."""
+    import torch
+    dev = rP.device
+    torch.cuda.synchronize()
+    work = torch.empty(capi.spgpuHellTransposeWorkBytes(n_rows, n_cols, slots), dtype=torch.uint8, device=dev)
+    lengths = torch.empty(max(n_cols, 1), dtype=torch.int32, device=dev)
+    longest, nnz, height = C.c_int(0), C.c_int(0), C.c_int(0)
+    ok = lambda status: status == capi.SPGPU_SUCCESS or (_ for _ in ()).throw(RuntimeError(f"status {status}"))
+    if ell_pitches is None:
+        ok(capi.spgpuHellTransposeLengthsDevice(handle, _dp(lengths), C.byref(longest), C.byref(nnz), _dp(rP), hack_size,
+                                                _dp(hack_offsets), _dp(rS), _dp(r_idx), n_rows, n_cols, base, slots, _dp(work)))
+    else:
+        ok(capi.spgpuEllTransposeLengthsDevice(handle, _dp(lengths), C.byref(longest), C.byref(nnz), _dp(rP), ell_pitches[1],
+                                               _dp(rS), _dp(r_idx), n_rows, n_cols, base, slots, _dp(work)))
+    hacks = (n_cols + t_hack_size - 1) // t_hack_size
+    t_offsets = torch.empty(max(hacks, 1), dtype=torch.int32, device=dev)
+    ok(capi.spgpuHellPlanDevice(handle, C.byref(height), _dp(t_offsets), t_hack_size, n_cols, _dp(lengths), _dp(work)))
+    t_slots = t_hack_size * height.value
+    t_values = torch.zeros(max(t_slots, 1), dtype=cM.dtype, device=dev)
+    t_indices = torch.zeros(max(t_slots, 1), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    code = capi.TYPE_CODE[letter]
+    if ell_pitches is None:
+        ok(capi.spgpuHellTransposeDevice(handle, _dp(t_values), _dp(t_indices), _dp(t_offsets), t_hack_size, t_base, _dp(cM), _dp(rP),
+                                         hack_size, _dp(hack_offsets), _dp(rS), _dp(r_idx), n_rows, n_cols, base, slots, code,
+                                         _dp(lengths), _dp(work)))
+    else:
+        ok(capi.spgpuEllTransposeDevice(handle, _dp(t_values), _dp(t_indices), _dp(t_offsets), t_hack_size, t_base, _dp(cM), _dp(rP),
+                                        ell_pitches[0], ell_pitches[1], _dp(rS), _dp(r_idx), n_rows, n_cols, base, slots, code,
+                                        _dp(lengths), _dp(work)))
+    torch.cuda.synchronize()
+    return dict(letter=letter, rows=n_cols, cols=n_rows, hack_size=t_hack_size, nnz=nnz.value, slots=t_slots, cM=t_values,
+                rP=t_indices, hack_offsets=t_offsets, rS=lengths, rIdx=None, base=t_base, longest=longest.value)
+
+
 def coo_to_ordered_hell_device(handle, n_rows, coo_rows, coo_cols, coo_vals, letter, hack_size=32, window=0, long_rows=0,
                                coo_base=0, hell_base=0, order=True, r_idx_given=None, aligned=False):
     """COO arrays in HBM (torch tensors) -> HELL in HBM with its rows ordered by length, all through the C ABI:
