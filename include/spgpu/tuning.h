@@ -200,6 +200,15 @@ void spgpuSetSpmvForm(spgpuHandle_t handle, int form);
 int spgpuGetSpmvForm(spgpuHandle_t handle);
 /* Diagnostic: the form (GATHER / STRIPS / XTILE / SWEEP) the most recent ELL/HELL SpMV call on this handle was launched in. */
 int spgpuGetLastSpmvForm(spgpuHandle_t handle);
+/* Diagnostic: which queue kernel the most recent ELL/HELL SpMV call on this handle launched, if it took the path for rows ordered by
+ * length (rIdx given, or SPGPU_DEEP_SPLIT=1): the 32-row sub-groups per workgroup (16 the gather shape, 32 the tiled, 64 the staged
+ * one) in the low byte, and the flags below.  0: that call did not take the ordered path.  spgpu?SpmvPrepare / Freeze launch no SpMV
+ * and leave the word as it was.  (Tiled and staged give the same bits of z: this is how to tell them apart from outside.) */
+#define SPGPU_ORDERED_SUBS_MASK 0xFF
+#define SPGPU_ORDERED_PLAN   0x100 /* the kernel that runs from a plan (one launch; also the stateless launch of a stream without a deep list) */
+#define SPGPU_ORDERED_PACKED 0x200 /* ... reading a frozen matrix' 16-bit column words */
+#define SPGPU_ORDERED_DEEP   0x400 /* no plan: the two deep kernels were launched behind the queue kernel */
+int spgpuGetLastOrderedLaunch(spgpuHandle_t handle);
 
 /*
  * The answer AUTO would settle on for ONE matrix, for a caller who wants to hold it instead of leaving it to AUTO's table

@@ -372,6 +372,9 @@ def plan_counts(handle):
     spgpuSpmvPlanCounts(handle, C.byref(u), C.byref(b), C.byref(s))
     return u.value, b.value, s.value
 spgpuGetLastSpmvForm = _decl("spgpuGetLastSpmvForm", i32, [Handle])
+# which queue kernel the last call launched on the ordered path (0: it took another path): sub-groups per workgroup | flags
+ORDERED_SUBS_MASK, ORDERED_PLAN, ORDERED_PACKED, ORDERED_DEEP = 0xFF, 0x100, 0x200, 0x400
+spgpuGetLastOrderedLaunch = _decl("spgpuGetLastOrderedLaunch", i32, [Handle])
 spgpuTuningVariantsBuilt = _decl("spgpuTuningVariantsBuilt", i32, [])
 spgpuHellSpmvForm = _decl("spgpuHellSpmvForm", i32, [Handle, i32, ptr, i32, ptr, ptr, i32, i32])
 spgpuEllSpmvForm = _decl("spgpuEllSpmvForm", i32, [Handle, i32, ptr, i32, ptr, i32, i32, i32])

@@ -323,6 +323,16 @@ void spgpuNoteSpmvForm(spgpuHandle_t pHandle, int form)
     __atomic_store_n(&spgpuPrivate(pHandle)->lastSpmvForm, form, __ATOMIC_RELAXED);
 }
 
+int spgpuGetLastOrderedLaunch(spgpuHandle_t pHandle)
+{
+    return __atomic_load_n(&spgpuPrivate(pHandle)->lastOrderedLaunch, __ATOMIC_RELAXED);
+}
+
+void spgpuNoteOrderedLaunch(spgpuHandle_t pHandle, int word)
+{
+    __atomic_store_n(&spgpuPrivate(pHandle)->lastOrderedLaunch, word, __ATOMIC_RELAXED);
+}
+
 /* ---- tuning knobs (include/spgpu/tuning.h) ---- */
 static SpgpuTuning tuning;
 static int tuningLoaded;

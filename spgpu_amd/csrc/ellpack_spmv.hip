@@ -156,7 +156,9 @@ static bool launchOrdered(spgpuHandle_t handle, hipStream_t stream, SlabArgs<T>&
     if (planned && launchPlanned<T, IS_HELL>(handle, stream, a, shape, tiledForm, noDeepList, SpmvCall::Run))
         return true;
     launchRagged<T, IS_HELL>(stream, a, shape, tiledForm);
-    if (deepKernelsFollow(IS_HELL, a.maxNnz, a.deepCap))
+    const bool deepFollow = deepKernelsFollow(IS_HELL, a.maxNnz, a.deepCap);
+    spgpuNoteOrderedLaunch(handle, queueShape(sizeof(T), tiledForm, shape).subs | (deepFollow ? SPGPU_ORDERED_DEEP : 0));
+    if (deepFollow)
         launchDeep<T, wideOf(sizeof(T)), IS_HELL>(stream, a);
     if (list.idle) {
         /* complete = the list has no user (core.c: a list may change hands) -- unless this launch is being captured: a graph
@@ -197,6 +199,7 @@ static void launchRowsAsTheyCome(spgpuHandle_t handle, hipStream_t stream, SlabA
     auto choose = [&](bool frozen) { return chooseRoute(form, wideOk, sizeof(T), IS_HELL, vote, a.avgNnzPerRow, a.maxNnz, frozen); };
     SpmvChoice c = choose(false);
     spgpuNoteSpmvForm(handle, c.noted);
+    spgpuNoteOrderedLaunch(handle, 0);
     if (vote.probeBehind)
         launchFormProbe<T, IS_HELL>(stream, a, wideOk);
     if (c.route == SpmvRoute::Wide) { /* a frozen matrix reads its 16-bit indices */

@@ -382,8 +382,9 @@ static void attachPlan(SlabArgs<T>& a, const SpgpuSpmvPlan* plan, bool tiled)
 
 /* raggedSpmvKernel<..., PLAN> over the blocks of rows and the workgroups of deep sub-groups. */
 template <typename T, bool IS_HELL>
-static void launchWithPlan(hipStream_t stream, SlabArgs<T>& a, bool tiled, bool staged)
+static void launchWithPlan(spgpuHandle_t handle, hipStream_t stream, SlabArgs<T>& a, bool tiled, bool staged)
 {
+    spgpuNoteOrderedLaunch(handle, queueShape(sizeof(T), tiled, staged ? kStagedShape : 0).subs | SPGPU_ORDERED_PLAN | (a.planPacked ? SPGPU_ORDERED_PACKED : 0));
     const unsigned grid = planGrid(a.planMainBlocks, a.planDeep);
     a.planDeepStride = planDeepStride(grid, planDeepBlocks(a.planDeep));
     withConstants([&](auto gather, auto packed, auto stagedToo) {
@@ -454,7 +455,7 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
             }
         } else if (plan && plan->state == SPGPU_PLAN_READY) {
             attachPlan(a, plan, tiled);
-            launchWithPlan<T, IS_HELL>(stream, a, tiled, staged); /* (under the lock: a retirement on another host thread waits for this launch to be queued) */
+            launchWithPlan<T, IS_HELL>(handle, stream, a, tiled, staged); /* (under the lock: a retirement on another host thread waits for this launch to be queued) */
             plan->uses += 1;
             h->planUses += 1;
             launched = true;
@@ -462,7 +463,7 @@ bool launchPlanned(spgpuHandle_t handle, hipStream_t stream, const SlabArgs<T>& 
         spgpuTablesUnlock(handle);
     }
     if (!launched && mustLaunch && !prepareOnly) {
-        launchWithPlan<T, IS_HELL>(stream, a, tiled, staged);
+        launchWithPlan<T, IS_HELL>(handle, stream, a, tiled, staged);
         launched = true;
     }
     return launched;

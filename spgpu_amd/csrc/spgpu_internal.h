@@ -52,6 +52,7 @@ typedef struct SpgpuPrivateHandle {
     int deepFallbacks;                        /* ordered SpMV calls on a stream without a list (spgpuDeepListFallbacks) */
     int deepRecycled;                         /* lists that changed hands (spgpuDeepListsRecycled) */
     int lastSpmvForm;         /* form of the most recent ELL/HELL SpMV launch (diagnostic, atomic) */
+    int lastOrderedLaunch;    /* SPGPU_ORDERED_* word of the most recent ELL/HELL SpMV launch, 0: not ordered (diagnostic, atomic) */
     /* per-matrix plans of the ELL/HELL SpMV with a row order (below; guarded by tablesLock) */
     struct SpgpuSpmvPlan* plans;                    /* [SPGPU_PLANS] */
     int* planPinned;                                /* pinned, SPGPU_PLANS * SPGPU_PLAN_WORDS ints */
@@ -243,6 +244,7 @@ static inline int spgpuStreamCapturing(hipStream_t stream)
 void spgpuDebugCheck(spgpuHandle_t h, const char* what);
 
 void spgpuNoteSpmvForm(spgpuHandle_t h, int form);
+void spgpuNoteOrderedLaunch(spgpuHandle_t h, int word); /* spgpuGetLastOrderedLaunch's answer (include/spgpu/tuning.h) */
 
 /* The feedback ints of the matrix identified by (key, rows): found or newly assigned (and zeroed); *calls = how many
  * SpMV calls have asked for this entry before. */

@@ -63,5 +63,5 @@ def test_hdia_h_dia_h_and_device_scalars_h_point_to_the_header():
 
 
 def test_the_headers_of_the_reference_surface_declare_what_they_declared():
-    assert len(declared_functions()) == 198
+    assert len(declared_functions()) == 199
     assert not NAMES & declared_functions()
