@@ -36,6 +36,8 @@
  *     spgpuHellPlanDevice(h, &height, hackOffsets, 32, rows, sortedLengths, work);
  *     spgpuCsrToHellDevice(h, cM, rP, hackOffsets, 32, base, rows, rowPtr, cols, vals, base, type, rIdx);
  *     spgpuDhellspmv(h, z, y, alpha, cM, rP, 32, hackOffsets, sortedLengths, rIdx, avg, rows, x, beta, base);
+ *
+ * The opposite direction, CSR arrays from a stored HELL or ELL matrix, is ext/to_csr_device.h.
  */
 #include "../core.h"
 

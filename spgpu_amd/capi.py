@@ -232,6 +232,29 @@ spgpuEllTransposeDevice = _decl("spgpuEllTransposeDevice", i32,
                                 [Handle, ptr, ptr, ptr, i32, i32, ptr, ptr, i32, i32, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr])
 
 
+# ---- ext/to_csr_device.h: CSR arrays from a stored HELL or ELL matrix, in HBM ---------------------------------------------
+spgpuToCsrWorkBytes = _decl("spgpuToCsrWorkBytes", C.c_size_t, [i32])
+# (handle, csrRowPtr, &nonZeros, &maxRowSize, csrBaseIndex, hackSize, hackOffsets, rS, rIdx, rows, slots, work)
+spgpuHellToCsrRowPtrDevice = _decl("spgpuHellToCsrRowPtrDevice", i32,
+                                   [Handle, ptr, C.POINTER(i32), C.POINTER(i32), i32, i32, ptr, ptr, ptr, i32, i32, ptr])
+# (handle, csrColIndices, csrValues, csrRowPtr, csrBaseIndex, cM, rP, hackSize, hackOffsets, rS, rIdx, rows, hellBaseIndex, valuesType)
+spgpuHellToCsrDevice = _decl("spgpuHellToCsrDevice", i32, [Handle, ptr, ptr, ptr, i32, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, i32])
+# (handle, csrRowPtr, &nonZeros, &maxRowSize, csrBaseIndex, ellIndicesPitch, rS, rIdx, rows, slots, work)
+spgpuEllToCsrRowPtrDevice = _decl("spgpuEllToCsrRowPtrDevice", i32,
+                                  [Handle, ptr, C.POINTER(i32), C.POINTER(i32), i32, i32, ptr, ptr, i32, i32, ptr])
+# (handle, csrColIndices, csrValues, csrRowPtr, csrBaseIndex, cM, rP, ellValuesPitch, ellIndicesPitch, rS, rIdx, rows, ellBaseIndex,
+#  valuesType)
+spgpuEllToCsrDevice = _decl("spgpuEllToCsrDevice", i32, [Handle, ptr, ptr, ptr, i32, ptr, ptr, i32, i32, ptr, ptr, i32, i32, i32])
+# not in the headers: the two fills behind the calls above, for the A/B tool and the tests that compare them
+# (..., valuesType, fill, maxBlocks): fill TO_CSR_FILL_PLAIN (one thread per storage row) or TO_CSR_FILL_TRANSPOSE (a wavefront per
+# 32 storage rows, TO_CSR_FILL_CHUNK slab columns per trip through LDS); maxBlocks > 0 caps the grid
+TO_CSR_FILL_PLAIN, TO_CSR_FILL_TRANSPOSE = 0, 1
+spgpuHellToCsrDeviceWith = _bind("spgpuHellToCsrDeviceWith", i32, spgpuHellToCsrDevice.argtypes + [i32, i32])
+spgpuEllToCsrDeviceWith = _bind("spgpuEllToCsrDeviceWith", i32, spgpuEllToCsrDevice.argtypes + [i32, i32])
+TO_CSR_FILL_CHUNK = _bind("spgpuToCsrFillChunk", i32, [])()
+TO_CSR_FILL_DEFAULT = _bind("spgpuToCsrDefaultFill", i32, [])()
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -175,6 +175,35 @@ def ell_transposed_coo(ell, r_idx=None, values_pitch=None):
                            values_pitch or ell["pitch"], r_idx, ell["base"])
 
 
+def slabs_to_csr(values, indices, row_lengths, n_rows, hack_offsets=None, hack_size=None, pitch=None, values_pitch=None, r_idx=None,
+                 src_base=0, csr_base=0):
+    """The CSR arrays include/spgpu/ext/to_csr_device.h defines, from host HELL arrays (hack_offsets and hack_size given) or host
+    ELL arrays (pitch of the indices given; values_pitch if it differs), restated in numpy: (row_ptr int32 of n_rows + 1 entries
+    starting at csr_base, cols int32, vals).  Storage row r is matrix row r_idx[r] (r without r_idx); the k-th entry of a matrix
+    row is slot k of its storage row; a column becomes index - src_base + csr_base.  Padding slots are never looked at."""
+    lengths = np.asarray(row_lengths, np.int64)[:n_rows]
+    r = np.arange(n_rows, dtype=np.int64)
+    if hack_offsets is not None:
+        first = np.asarray(hack_offsets, np.int64)[r // hack_size] + r % hack_size if n_rows else r
+        step = value_step = hack_size
+    else:
+        first, step, value_step = r, pitch, values_pitch or pitch
+    i = r if r_idx is None else np.asarray(r_idx, np.int64)[:n_rows]
+    by_matrix_row = np.zeros(n_rows, np.int64)
+    by_matrix_row[i] = lengths
+    row_ptr = np.zeros(n_rows + 1, np.int64)
+    np.cumsum(by_matrix_row, out=row_ptr[1:])
+    total = int(lengths.sum())
+    rr = np.repeat(r, lengths)
+    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(lengths) - lengths, lengths)
+    at = row_ptr[i[rr]] + k
+    cols = np.zeros(total, np.int32)
+    vals = np.zeros(total, np.asarray(values).dtype)
+    cols[at] = (np.asarray(indices)[first[rr] + k * step].astype(np.int64) - src_base + csr_base).astype(np.int32)
+    vals[at] = np.asarray(values)[first[rr] + k * value_step]
+    return (row_ptr + csr_base).astype(np.int32), cols, vals
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
