@@ -37,7 +37,8 @@
  *     spgpuCsrToHellDevice(h, cM, rP, hackOffsets, 32, base, rows, rowPtr, cols, vals, base, type, rIdx);
  *     spgpuDhellspmv(h, z, y, alpha, cM, rP, 32, hackOffsets, sortedLengths, rIdx, avg, rows, x, beta, base);
  *
- * The opposite direction, CSR arrays from a stored HELL or ELL matrix, is ext/to_csr_device.h.
+ * The opposite direction, CSR arrays from a stored HELL or ELL matrix, is ext/to_csr_device.h.  New coefficients for a matrix
+ * these calls built, its pattern unchanged (no column index read or written again), are ext/update_device.h.
  */
 #include "../core.h"
 

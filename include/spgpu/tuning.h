@@ -86,7 +86,8 @@ int spgpuEllSpmvPrepare(spgpuHandle_t handle, spgpuType_t type, const void* cM, 
  * FROZEN matrices (no counterpart in the reference).  An iterative solver multiplies by one matrix thousands of times
  * (hellPerf.cpp:301-313 is that loop); its index arrays never change in between.  A caller who can PROMISE that -- rP, rS,
  * hackOffsets and rIdx of this matrix stay byte for byte as they are until spgpuSpmvThaw (cM may change at any time: the
- * coefficients are always read from the caller's array) -- lets the library keep what it derives from them: spgpu?SpmvFreeze
+ * coefficients are always read from the caller's array; the calls of ext/update_device.h replace them on the device, with no
+ * Thaw -- an ADOPTED matrix is thawed first) -- lets the library keep what it derives from them: spgpu?SpmvFreeze
  * stores the column indices of the matrix as 16-bit offsets (2 bytes per slot of rP; 0xFFFF where a column lies out of reach:
  * such entries are still read from rP):
  *   with a row order (rIdx != NULL): what spgpu?SpmvPrepare does, then the copy with the matrix' plan, counted from the first

@@ -255,6 +255,24 @@ TO_CSR_FILL_CHUNK = _bind("spgpuToCsrFillChunk", i32, [])()
 TO_CSR_FILL_DEFAULT = _bind("spgpuToCsrDefaultFill", i32, [])()
 
 
+# ---- ext/update_device.h: new coefficients for a stored HELL or ELL matrix, pattern unchanged, in HBM ------------------------
+# (handle, hellValues, hackOffsets, hackSize, rows, csrRowPtr, csrValues, csrBaseIndex, valuesType, rIdx)
+spgpuCsrToHellValuesDevice = _decl("spgpuCsrToHellValuesDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, i32, i32, ptr])
+# (handle, ellValues, ellValuesPitch, rows, csrRowPtr, csrValues, csrBaseIndex, valuesType, rIdx)
+spgpuCsrToEllValuesDevice = _decl("spgpuCsrToEllValuesDevice", i32, [Handle, ptr, i32, i32, ptr, ptr, i32, i32, ptr])
+spgpuInvertRowOrderDevice = _decl("spgpuInvertRowOrderDevice", i32, [Handle, ptr, ptr, i32])
+# (handle, alpha, cM, rP, hackSize, hackOffsets, rS, rowOf, rows, nnz, aI, aJ, aVal, baseIndex)
+hellcsput = {}
+for _L, _T in SCALAR.items():
+    hellcsput[_L] = _decl(f"spgpu{_L}hellcsput", None, [Handle, _T, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, ptr, ptr, ptr, i32])
+# not in the headers: the two refills behind the value calls, for the A/B tool and the tests that compare them
+# (..., rIdx, fill, maxBlocks): fill UPDATE_FILL_PLAIN (one thread per row), UPDATE_FILL_TRANSPOSE (a wavefront per 32 rows through
+# LDS, 16-byte stores where the slab is aligned) or < 0 for the public call's choice; maxBlocks > 0 caps the grid
+UPDATE_FILL_PLAIN, UPDATE_FILL_TRANSPOSE = 0, 1
+spgpuCsrToHellValuesDeviceWith = _bind("spgpuCsrToHellValuesDeviceWith", i32, spgpuCsrToHellValuesDevice.argtypes + [i32, i32])
+spgpuCsrToEllValuesDeviceWith = _bind("spgpuCsrToEllValuesDeviceWith", i32, spgpuCsrToEllValuesDevice.argtypes + [i32, i32])
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])
