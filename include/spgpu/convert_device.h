@@ -24,6 +24,7 @@
  * hackOffsets from spgpuHellPlanDevice below, for which `work` of spgpuCooConvertWorkBytes(rowsCount, 0) bytes is enough.
  * The transpose of a stored HELL or ELL matrix is built the same way, as a HELL matrix, by ext/transpose_device.h.
  * The way back -- CSR arrays from a stored HELL or ELL matrix -- is ext/to_csr_device.h.
+ * A list in which one matrix entry appears several times and the SUMS are wanted (assembly) goes through ext/assemble_device.h.
  */
 #include "core.h"
 

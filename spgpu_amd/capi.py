@@ -273,6 +273,27 @@ spgpuCsrToHellValuesDeviceWith = _bind("spgpuCsrToHellValuesDeviceWith", i32, sp
 spgpuCsrToEllValuesDeviceWith = _bind("spgpuCsrToEllValuesDeviceWith", i32, spgpuCsrToEllValuesDevice.argtypes + [i32, i32])
 
 
+# ---- ext/assemble_device.h: a COO list with duplicates summed into CSR arrays, in HBM ---------------------------------------
+spgpuCooAssembleWorkBytes = _decl("spgpuCooAssembleWorkBytes", C.c_size_t, [i32, i32, i32])
+# (handle, &uniqueCount, csrRowPtr, perm, segPtr, rows, cols, nnz, cooRowIndices, cooColsIndices, cooBaseIndex, csrBaseIndex, work)
+spgpuCooAssemblePlanDevice = _decl("spgpuCooAssemblePlanDevice", i32,
+                                   [Handle, C.POINTER(i32), ptr, ptr, ptr, i32, i32, i32, ptr, ptr, i32, i32, ptr])
+# (handle, csrColIndices, csrValues, uniqueCount, nnz, cooColsIndices, cooValues, cooBaseIndex, csrBaseIndex, valuesType, perm, segPtr)
+spgpuCooAssembleDevice = _decl("spgpuCooAssembleDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, i32, i32, i32, ptr, ptr])
+# (handle, csrValues, uniqueCount, nnz, cooValues, valuesType, perm, segPtr)
+spgpuCooAssembleValuesDevice = _decl("spgpuCooAssembleValuesDevice", i32, [Handle, ptr, i32, i32, ptr, i32, ptr, ptr])
+# not in the headers: the two fills behind the calls above, for the A/B tool and the tests that compare them
+# (..., segPtr, fill, maxBlocks): fill ASSEMBLE_FILL_PLAIN (one thread per matrix entry), ASSEMBLE_FILL_STAGED (a workgroup per
+# ASSEMBLE_TILE entries, ASSEMBLE_CHUNK positions of perm per trip through LDS, counted from the tile's first position) or < 0 for
+# the public call's choice; maxBlocks > 0 caps the grid
+ASSEMBLE_FILL_PLAIN, ASSEMBLE_FILL_STAGED = 0, 1
+spgpuCooAssembleDeviceWith = _bind("spgpuCooAssembleDeviceWith", i32, spgpuCooAssembleDevice.argtypes + [i32, i32])
+spgpuCooAssembleValuesDeviceWith = _bind("spgpuCooAssembleValuesDeviceWith", i32, spgpuCooAssembleValuesDevice.argtypes + [i32, i32])
+ASSEMBLE_FILL_DEFAULT = _bind("spgpuCooAssembleDefaultFill", i32, [])()
+ASSEMBLE_TILE = _bind("spgpuCooAssembleTile", i32, [])()
+ASSEMBLE_CHUNK = _bind("spgpuCooAssembleChunk", i32, [])()
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -204,6 +204,34 @@ def slabs_to_csr(values, indices, row_lengths, n_rows, hack_offsets=None, hack_s
     return (row_ptr + csr_base).astype(np.int32), cols, vals
 
 
+def coo_assemble(n_rows, n_cols, coo_rows, coo_cols, coo_vals, coo_base=0, csr_base=0):
+    """The arrays include/spgpu/ext/assemble_device.h defines, restated in numpy: (row_ptr, perm, seg_ptr, cols, vals) of a COO list
+    of contributions in which a matrix entry may appear several times.  perm is a stable sort of the list by (row, column); seg_ptr
+    has one more element than there are distinct (row, column) pairs; row_ptr int32 of n_rows + 1 elements starting at csr_base;
+    a column becomes index - coo_base + csr_base; vals[u] is the sum of entry u's contributions in perm order, left to right, each
+    addition rounded in the dtype of coo_vals.  The sums are accumulated by depth -- step k adds the k-th contribution of every
+    entry that has one -- and start from the first contribution, which is copied as it is."""
+    rows = np.asarray(coo_rows, np.int64) - coo_base
+    cols = np.asarray(coo_cols, np.int64) - coo_base
+    vals = np.asarray(coo_vals)
+    if rows.size and (rows.min() < 0 or rows.max() >= n_rows or cols.min() < 0 or cols.max() >= n_cols):
+        raise ValueError("an entry lies outside the matrix")
+    perm = np.lexsort((cols, rows)).astype(np.int32)              # lexsort is stable: equal pairs keep their COO order
+    sorted_rows, sorted_cols = rows[perm], cols[perm]
+    head = np.ones(perm.size, bool)
+    head[1:] = (sorted_rows[1:] != sorted_rows[:-1]) | (sorted_cols[1:] != sorted_cols[:-1])
+    first = np.flatnonzero(head)
+    seg_ptr = np.concatenate((first, [perm.size])).astype(np.int32)
+    row_ptr = (np.searchsorted(sorted_rows[first], np.arange(n_rows + 1), side="left") + csr_base).astype(np.int32)
+    out_cols = (sorted_cols[first] + csr_base).astype(np.int32)
+    out_vals = vals[perm[first]].copy()
+    lengths = np.diff(seg_ptr.astype(np.int64))
+    for k in range(1, int(lengths.max()) if lengths.size else 0):
+        more = np.flatnonzero(lengths > k)
+        out_vals[more] = out_vals[more] + vals[perm[first[more] + k]]
+    return row_ptr, perm, seg_ptr, out_cols, out_vals
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
