@@ -59,6 +59,9 @@
  *     (step)  spgpuCooAssembleValuesDevice(h, csrVals, unique, nnz, cooVals, type, perm, segPtr);
  *             spgpuCsrToHellValuesDevice(h, cM, hackOffsets, 32, rows, rowPtr, csrVals, base, type, NULL);
  *             spgpuDhellspmv(...);
+ *
+ * The assembled CSR arrays are also what the sparse product of ext/spgemm_device.h takes on either side (its B wants ascending
+ * columns): a Galerkin operator P^T * A * P follows the assembly, and its values-only pass this one's, without leaving HBM.
  */
 #include "../core.h"
 

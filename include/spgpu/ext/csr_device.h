@@ -38,7 +38,8 @@
  *     spgpuDhellspmv(h, z, y, alpha, cM, rP, 32, hackOffsets, sortedLengths, rIdx, avg, rows, x, beta, base);
  *
  * The opposite direction, CSR arrays from a stored HELL or ELL matrix, is ext/to_csr_device.h.  New coefficients for a matrix
- * these calls built, its pattern unchanged (no column index read or written again), are ext/update_device.h.
+ * these calls built, its pattern unchanged (no column index read or written again), are ext/update_device.h.  The product of
+ * two CSR matrices, whose result these calls take, is ext/spgemm_device.h.
  */
 #include "../core.h"
 

@@ -294,6 +294,29 @@ ASSEMBLE_TILE = _bind("spgpuCooAssembleTile", i32, [])()
 ASSEMBLE_CHUNK = _bind("spgpuCooAssembleChunk", i32, [])()
 
 
+# ---- ext/spgemm_device.h: the sparse product C = A * B on CSR arrays with one common base, in HBM ----------------------------
+spgpuCsrSpgemmWorkBytes = _decl("spgpuCsrSpgemmWorkBytes", C.c_size_t, [i32, i32, i32])
+# (handle, &productsCount, aRows, aColumns, aRowPtr, aColIndices, bRowPtr, baseIndex, work)
+spgpuCsrSpgemmProductsDevice = _decl("spgpuCsrSpgemmProductsDevice", i32, [Handle, C.POINTER(i32), i32, i32, ptr, ptr, ptr, i32, ptr])
+# (handle, &cNonZerosCount, cRowPtr, aRows, aColumns, bColumns, aRowPtr, aColIndices, bRowPtr, bColIndices, baseIndex, productsCount, work)
+spgpuCsrSpgemmPlanDevice = _decl("spgpuCsrSpgemmPlanDevice", i32,
+                                 [Handle, C.POINTER(i32), ptr, i32, i32, i32, ptr, ptr, ptr, ptr, i32, i32, ptr])
+# (handle, cColIndices, cValues, cNonZerosCount, aRows, aRowPtr, aColIndices, aValues, bRowPtr, bColIndices, bValues, cRowPtr, baseIndex,
+#  valuesType, work)
+spgpuCsrSpgemmDevice = _decl("spgpuCsrSpgemmDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32, ptr])
+# (handle, cValues, aRows, aRowPtr, aColIndices, aValues, bRowPtr, bColIndices, bValues, cRowPtr, cColIndices, baseIndex, valuesType)
+spgpuCsrSpgemmValuesDevice = _decl("spgpuCsrSpgemmValuesDevice", i32, [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
+# not in the headers: the two fills behind the calls above, for the A/B tool and the tests that compare them
+# (..., fill, maxBlocks): fill SPGEMM_FILL_PLAIN (one thread per entry of C), SPGEMM_FILL_STAGED (a wavefront per row of C, a row of
+# at most SPGEMM_ROW_CAP entries accumulated in LDS, a longer one by the plain method) or < 0 for the public call's choice;
+# maxBlocks > 0 caps the grid
+SPGEMM_FILL_PLAIN, SPGEMM_FILL_STAGED = 0, 1
+spgpuCsrSpgemmDeviceWith = _bind("spgpuCsrSpgemmDeviceWith", i32, spgpuCsrSpgemmDevice.argtypes + [i32, i32])
+spgpuCsrSpgemmValuesDeviceWith = _bind("spgpuCsrSpgemmValuesDeviceWith", i32, spgpuCsrSpgemmValuesDevice.argtypes + [i32, i32])
+SPGEMM_FILL_DEFAULT = _bind("spgpuCsrSpgemmDefaultFill", i32, [])()
+SPGEMM_ROW_CAP = _bind("spgpuCsrSpgemmRowCap", i32, [])()
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

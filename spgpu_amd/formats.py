@@ -232,6 +232,66 @@ def coo_assemble(n_rows, n_cols, coo_rows, coo_cols, coo_vals, coo_base=0, csr_b
     return row_ptr, perm, seg_ptr, out_cols, out_vals
 
 
+def csr_spgemm(a_ptr, a_cols, a_vals, b_ptr, b_cols, b_vals, n_b_cols, base=0):
+    """The arrays include/spgpu/ext/spgemm_device.h defines, restated in numpy: (products, c_ptr, c_cols, c_vals) of C = A * B, all
+    three CSR in `base`.  A's rows in any order, duplicates allowed; B's rows strictly ascending.  The pattern is symbolic (an entry
+    whose terms cancel stays); c_vals[u] = ((0 + p0) + p1) + ..., the products taken over A's row in storage order, each product
+    rounded in the dtype of the values and each addition rounded again.  A complex product is computed on the real views -- re =
+    ar*br - ai*bi, im = ar*bi + ai*br, six separately rounded operations -- so that no library fuses anything.  One Python step per
+    stored entry of A: a restatement for tests, not a tool."""
+    a_ptr, b_ptr = np.asarray(a_ptr, np.int64) - base, np.asarray(b_ptr, np.int64) - base
+    a_cols, b_cols = np.asarray(a_cols, np.int64) - base, np.asarray(b_cols, np.int64) - base
+    a_vals, b_vals = np.asarray(a_vals), np.asarray(b_vals)
+    dtype = a_vals.dtype
+    if b_vals.dtype != dtype:
+        raise ValueError("A and B hold different types")
+    n_rows, n_inner = a_ptr.size - 1, b_ptr.size - 1
+    if a_cols.size and (a_cols.min() < 0 or a_cols.max() >= n_inner):
+        raise ValueError("a column of A names no row of B")
+    if b_cols.size and (b_cols.min() < 0 or b_cols.max() >= n_b_cols):
+        raise ValueError("a column of B lies outside the matrix")
+    inside_a_row = np.ones(max(b_cols.size - 1, 0), bool)
+    inside_a_row[b_ptr[1:-1][(b_ptr[1:-1] > 0) & (b_ptr[1:-1] < b_cols.size)] - 1] = False
+    if np.any((np.diff(b_cols) <= 0) & inside_a_row):
+        raise ValueError("a row of B does not ascend strictly")
+    real = dtype.kind != "c"
+    part = dtype if real else np.dtype("f%d" % (dtype.itemsize // 2))
+    b_len = np.diff(b_ptr)
+    products = 0
+    c_ptr = np.zeros(n_rows + 1, np.int64)
+    all_cols, all_vals = [], []
+    for i in range(n_rows):
+        entries = range(a_ptr[i], a_ptr[i + 1])
+        products += int(b_len[a_cols[a_ptr[i]:a_ptr[i + 1]]].sum())
+        named = [b_cols[b_ptr[a_cols[e]]:b_ptr[a_cols[e] + 1]] for e in entries]
+        cols = np.unique(np.concatenate(named)) if named else np.zeros(0, np.int64)
+        if real:
+            acc = np.zeros(cols.size, dtype)
+        else:
+            acc_re, acc_im = np.zeros(cols.size, part), np.zeros(cols.size, part)
+        for e, js in zip(entries, named):
+            at = np.searchsorted(cols, js)                    # distinct slots: B's row has no duplicate column
+            b = b_vals[b_ptr[a_cols[e]]:b_ptr[a_cols[e] + 1]]
+            if real:
+                acc[at] = acc[at] + a_vals[e] * b             # the product array is rounded before the addition reads it
+            else:
+                ar, ai = part.type(a_vals[e].real), part.type(a_vals[e].imag)
+                br, bi = np.ascontiguousarray(b.real), np.ascontiguousarray(b.imag)
+                rr, ii, ri, ir = ar * br, ai * bi, ar * bi, ai * br
+                re, im = rr - ii, ri + ir
+                acc_re[at] = acc_re[at] + re
+                acc_im[at] = acc_im[at] + im
+        if not real:
+            acc = np.empty(cols.size, dtype)
+            acc.real, acc.imag = acc_re, acc_im
+        c_ptr[i + 1] = c_ptr[i] + cols.size
+        all_cols.append(cols)
+        all_vals.append(acc)
+    c_cols = np.concatenate(all_cols) if all_cols else np.zeros(0, np.int64)
+    c_vals = np.concatenate(all_vals) if all_vals else np.zeros(0, dtype)
+    return products, (c_ptr + base).astype(np.int32), (c_cols + base).astype(np.int32), np.ascontiguousarray(c_vals.astype(dtype, copy=False))
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
