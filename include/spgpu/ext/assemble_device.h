@@ -62,6 +62,7 @@
  *
  * The assembled CSR arrays are also what the sparse product of ext/spgemm_device.h takes on either side (its B wants ascending
  * columns): a Galerkin operator P^T * A * P follows the assembly, and its values-only pass this one's, without leaving HBM.
+ * Two separately assembled matrices -- a mass and a stiffness matrix -- are added as M + dt * K by ext/add_device.h.
  */
 #include "../core.h"
 

@@ -39,7 +39,7 @@
  *
  * The opposite direction, CSR arrays from a stored HELL or ELL matrix, is ext/to_csr_device.h.  New coefficients for a matrix
  * these calls built, its pattern unchanged (no column index read or written again), are ext/update_device.h.  The product of
- * two CSR matrices, whose result these calls take, is ext/spgemm_device.h.
+ * two CSR matrices, whose result these calls take, is ext/spgemm_device.h.  Their sum alpha * A + beta * B is ext/add_device.h.
  */
 #include "../core.h"
 

@@ -68,6 +68,8 @@
  *     (step)  spgpuCsrSpgemmValuesDevice(h, rVal, ptRows, ptPtr, ptIdx, ptVal, aPtr, aIdx, aVal, rPtr, rIdx, base, type);
  *             spgpuCsrSpgemmValuesDevice(h, cVal, ptRows, rPtr, rIdx, rVal, pPtr, pIdx, pVal, cPtr, cIdx, base, type);
  *             spgpuCsrToHellValuesDevice(...);  spgpuDhellspmv(...);
+ *
+ * The sum of two CSR matrices -- the smoothed prolongator P = T - omega * (A * T) after this product -- is ext/add_device.h.
  */
 #include "../core.h"
 

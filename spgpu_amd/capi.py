@@ -317,6 +317,30 @@ SPGEMM_FILL_DEFAULT = _bind("spgpuCsrSpgemmDefaultFill", i32, [])()
 SPGEMM_ROW_CAP = _bind("spgpuCsrSpgemmRowCap", i32, [])()
 
 
+# ---- ext/add_device.h: the sparse sum C = alpha * A + beta * B on CSR arrays with one common base, in HBM -------------------
+spgpuCsrAddWorkBytes = _decl("spgpuCsrAddWorkBytes", C.c_size_t, [i32])
+# (handle, &cNonZerosCount, cRowPtr, rows, columns, aRowPtr, aColIndices, bRowPtr, bColIndices, baseIndex, work)
+spgpuCsrAddPlanDevice = _decl("spgpuCsrAddPlanDevice", i32, [Handle, C.POINTER(i32), ptr, i32, i32, ptr, ptr, ptr, ptr, i32, ptr])
+# (handle, cColIndices, cValues, cNonZerosCount, rows, &alpha (host), aRowPtr, aColIndices, aValues, &beta (host), bRowPtr, bColIndices,
+#  bValues, cRowPtr, baseIndex, valuesType)
+spgpuCsrAddDevice = _decl("spgpuCsrAddDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
+# (handle, cValues, rows, &alpha, aRowPtr, aColIndices, aValues, &beta, bRowPtr, bColIndices, bValues, cRowPtr, baseIndex, valuesType):
+# alpha and beta on the host, read at the call; in spgpuCsrAddValuesDeviceScalars in device memory, read by the kernel
+spgpuCsrAddValuesDevice = _decl("spgpuCsrAddValuesDevice", i32, [Handle, ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32])
+spgpuCsrAddValuesDeviceScalars = _decl("spgpuCsrAddValuesDeviceScalars", i32, list(spgpuCsrAddValuesDevice.argtypes))
+# not in the headers: the two fills behind the calls above, for the A/B tool and the tests that compare them
+# (..., fill, maxBlocks): fill ADD_FILL_PLAIN (one thread per stored entry of A and of B, rows and ranks by bisection in global
+# memory), ADD_FILL_STAGED (a workgroup per ADD_TILE entries of C, the column slices of its rows in LDS, a last row of more than
+# ADD_ROW_CAP entries by the plain method) or < 0 for the public call's choice; maxBlocks > 0 caps the grid
+ADD_FILL_PLAIN, ADD_FILL_STAGED = 0, 1
+spgpuCsrAddDeviceWith = _bind("spgpuCsrAddDeviceWith", i32, spgpuCsrAddDevice.argtypes + [i32, i32])
+spgpuCsrAddValuesDeviceWith = _bind("spgpuCsrAddValuesDeviceWith", i32, spgpuCsrAddValuesDevice.argtypes + [i32, i32])
+spgpuCsrAddValuesDeviceScalarsWith = _bind("spgpuCsrAddValuesDeviceScalarsWith", i32, spgpuCsrAddValuesDevice.argtypes + [i32, i32])
+ADD_FILL_DEFAULT = _bind("spgpuCsrAddDefaultFill", i32, [])()
+ADD_TILE = _bind("spgpuCsrAddTile", i32, [])()
+ADD_ROW_CAP = _bind("spgpuCsrAddRowCap", i32, [])()
+
+
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])
 oellOrderAligned = _decl("oellOrderAligned", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -292,6 +292,63 @@ def csr_spgemm(a_ptr, a_cols, a_vals, b_ptr, b_cols, b_vals, n_b_cols, base=0):
     return products, (c_ptr + base).astype(np.int32), (c_cols + base).astype(np.int32), np.ascontiguousarray(c_vals.astype(dtype, copy=False))
 
 
+def _scaled(scalar, vals):
+    """scalar * vals as include/spgpu/ext/add_device.h defines it: rounded once in the dtype of vals; a complex product computed on the
+    real views -- re = sr*vr - si*vi, im = sr*vi + si*vr, six separately rounded operations -- so that no library fuses anything."""
+    dtype = vals.dtype
+    if dtype.kind != "c":
+        return dtype.type(scalar) * vals
+    part = np.dtype("f%d" % (dtype.itemsize // 2))
+    s = np.asarray(scalar, dtype)[()]
+    sr, si = part.type(s.real), part.type(s.imag)
+    vr, vi = np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)
+    rr, ii, ri, ir = sr * vr, si * vi, sr * vi, si * vr
+    out = np.empty(vals.size, dtype)
+    out.real, out.imag = rr - ii, ri + ir
+    return out
+
+
+def csr_add(a_ptr, a_cols, a_vals, b_ptr, b_cols, b_vals, n_cols, alpha, beta, base=0):
+    """The arrays include/spgpu/ext/add_device.h defines, restated in numpy: (c_ptr, c_cols, c_vals) of C = alpha * A + beta * B, all
+    three CSR in `base`, A and B both of n_cols columns with strictly ascending rows.  The pattern is the union (an entry whose terms
+    cancel stays).  Where both store the entry c = (alpha * a) + (beta * b), each product rounded in the dtype of the values (_scaled)
+    and the sum rounded again (complex: componentwise); where one stores it, its product alone.  alpha and beta are rounded to that
+    dtype first.  ValueError on what spgpuCsrAddPlanDevice refuses."""
+    a_ptr, b_ptr = np.asarray(a_ptr, np.int64) - base, np.asarray(b_ptr, np.int64) - base
+    a_cols, b_cols = np.asarray(a_cols, np.int64) - base, np.asarray(b_cols, np.int64) - base
+    a_vals, b_vals = np.asarray(a_vals), np.asarray(b_vals)
+    dtype = a_vals.dtype
+    if b_vals.dtype != dtype:
+        raise ValueError("A and B hold different types")
+    if a_ptr.size != b_ptr.size:
+        raise ValueError("A and B have different numbers of rows")
+    n_rows = a_ptr.size - 1
+    keys = []
+    for name, ptr, cols in (("A", a_ptr, a_cols), ("B", b_ptr, b_cols)):
+        cols = cols[:ptr[-1]]
+        if cols.size and (cols.min() < 0 or cols.max() >= n_cols):
+            raise ValueError(f"a column of {name} lies outside the matrix")
+        key = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(ptr)) * max(int(n_cols), 1) + cols
+        if np.any(np.diff(key) <= 0):                          # rows never descend, so only a row's own order can fail
+            raise ValueError(f"a row of {name} does not ascend strictly")
+        keys.append(key)
+    union = np.union1d(keys[0], keys[1])
+    if union.size > 2 ** 31 - 1:
+        raise ValueError("more than INT_MAX entries in the union")
+    at_a, at_b = np.searchsorted(union, keys[0]), np.searchsorted(union, keys[1])
+    from_a, from_b = _scaled(alpha, a_vals[:keys[0].size]), _scaled(beta, b_vals[:keys[1].size])
+    in_a, in_b = np.zeros(union.size, bool), np.zeros(union.size, bool)
+    in_a[at_a], in_b[at_b] = True, True
+    c_vals = np.zeros(union.size, dtype)
+    c_vals[at_a] = from_a                                      # the product alone where the other matrix has nothing
+    c_vals[at_b] = from_b
+    both_a, both_b = in_b[at_a], in_a[at_b]                    # the same entries of C in the same (ascending) order
+    c_vals[at_a[both_a]] = from_a[both_a] + from_b[both_b]
+    c_ptr = np.searchsorted(union // max(int(n_cols), 1), np.arange(n_rows + 1), side="left")
+    c_cols = union % max(int(n_cols), 1)
+    return (c_ptr + base).astype(np.int32), (c_cols + base).astype(np.int32), np.ascontiguousarray(c_vals)
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
