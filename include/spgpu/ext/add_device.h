@@ -70,6 +70,8 @@
  *             spgpuCsrRowLengthsDevice / spgpuHellPlanDevice / spgpuCsrToHellDevice on C
  *     (step)  spgpuCsrAddValuesDevice(h, cVal, rows, &one, mPtr, mIdx, mVal, &dt, kPtr, kIdx, kVal, cPtr, base, type);
  *             spgpuCsrToHellValuesDevice(...);  spgpuDhellspmv(...);
+ *
+ * Solving with a triangle of the CSR matrix this builds -- a Gauss-Seidel sweep on M + dt * K -- is ext/trsv_device.h.
  */
 #include "../core.h"
 

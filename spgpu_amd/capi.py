@@ -340,6 +340,22 @@ ADD_FILL_DEFAULT = _bind("spgpuCsrAddDefaultFill", i32, [])()
 ADD_TILE = _bind("spgpuCsrAddTile", i32, [])()
 ADD_ROW_CAP = _bind("spgpuCsrAddRowCap", i32, [])()
 
+# ---- ext/trsv_device.h: the sparse triangular solve x = T^-1 * b on CSR arrays, level-scheduled, in HBM ------------------------
+TRSV_LOWER, TRSV_UPPER = 0, 1
+TRSV_DIAG_STORED, TRSV_DIAG_UNIT = 0, 1
+spgpuCsrTrsvWorkBytes = _decl("spgpuCsrTrsvWorkBytes", C.c_size_t, [i32])
+# (handle, &levelsCount, rowOrder, levelPtr, levelPtrHost (host), rows, rowPtr, colIndices, baseIndex, side, diag, work)
+spgpuCsrTrsvPlanDevice = _decl("spgpuCsrTrsvPlanDevice", i32, [Handle, C.POINTER(i32), ptr, ptr, C.POINTER(i32), i32, ptr, ptr, i32, i32, i32, ptr])
+# (handle, x, b, rows, levelsCount, rowOrder, levelPtr, levelPtrHost (host), rowPtr, colIndices, values, baseIndex, side, diag, valuesType)
+spgpuCsrTrsvDevice = _decl("spgpuCsrTrsvDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, C.POINTER(i32), ptr, ptr, ptr, i32, i32, i32, i32])
+# not in the headers: the two solves behind the call above, for the A/B tool and the tests that compare them
+# (..., solve, maxBlocks): solve TRSV_SOLVE_PLAIN (one launch per level), TRSV_SOLVE_CHAINED (a run of levels of at most
+# TRSV_CHAIN_WIDTH rows each is one launch of one workgroup) or < 0 for the public call's choice; maxBlocks > 0 caps a level's grid
+TRSV_SOLVE_PLAIN, TRSV_SOLVE_CHAINED = 0, 1
+spgpuCsrTrsvDeviceWith = _bind("spgpuCsrTrsvDeviceWith", i32, spgpuCsrTrsvDevice.argtypes + [i32, i32])
+TRSV_SOLVE_DEFAULT = _bind("spgpuCsrTrsvDefaultSolve", i32, [])()
+TRSV_CHAIN_WIDTH = _bind("spgpuCsrTrsvChainWidth", i32, [])()
+
 
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])

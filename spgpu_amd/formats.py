@@ -349,6 +349,93 @@ def csr_add(a_ptr, a_cols, a_vals, b_ptr, b_cols, b_vals, n_cols, alpha, beta, b
     return (c_ptr + base).astype(np.int32), (c_cols + base).astype(np.int32), np.ascontiguousarray(c_vals)
 
 
+def _trsv_rows(row_ptr, col, base, side, diag):
+    """The checks of spgpuCsrTrsvPlanDevice; (n_rows, 0-based row_ptr, 0-based col) as int64.  ValueError on each refusal."""
+    if side not in (capi.TRSV_LOWER, capi.TRSV_UPPER) or diag not in (capi.TRSV_DIAG_STORED, capi.TRSV_DIAG_UNIT):
+        raise ValueError("side is TRSV_LOWER or TRSV_UPPER, diag TRSV_DIAG_STORED or TRSV_DIAG_UNIT")
+    ptr = np.asarray(row_ptr, np.int64) - base
+    n_rows = ptr.size - 1
+    col = np.asarray(col, np.int64)[:ptr[-1]] - base
+    if col.size and (col.min() < 0 or col.max() >= n_rows):
+        raise ValueError("a column lies outside the matrix")
+    if diag == capi.TRSV_DIAG_STORED:
+        row_of = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(ptr))
+        diagonals = np.bincount(row_of[col == row_of], minlength=n_rows)
+        if np.any(diagonals == 0):
+            raise ValueError("a row stores no diagonal")
+        if np.any(diagonals > 1):
+            raise ValueError("a row stores its diagonal twice")
+    return n_rows, ptr, col
+
+
+def csr_trsv_plan(row_ptr, col, base=0, side=capi.TRSV_LOWER, diag=capi.TRSV_DIAG_STORED):
+    """The arrays include/spgpu/ext/trsv_device.h defines, restated: (levels, row_order, level_ptr) of the square CSR matrix in
+    `base`.  level(i) = 0 if row i stores no off-diagonal entry on `side`, else 1 + the largest level over those entries (symbolic: a
+    stored zero counts); row_order lists the 0-based rows by (level, row) ascending; level_ptr[l] = the number of rows in levels
+    < l, levels + 1 ints.  ValueError on what spgpuCsrTrsvPlanDevice refuses.  One Python step per row: a restatement for tests."""
+    n_rows, ptr, col = _trsv_rows(row_ptr, col, base, side, diag)
+    level = np.zeros(n_rows, np.int64)
+    lower = side == capi.TRSV_LOWER
+    for i in (range(n_rows) if lower else range(n_rows - 1, -1, -1)):
+        js = col[ptr[i]:ptr[i + 1]]
+        js = js[js < i] if lower else js[js > i]
+        level[i] = 1 + level[js].max() if js.size else 0
+    levels = int(level.max()) + 1 if n_rows > 0 else 0
+    row_order = np.lexsort((np.arange(n_rows), level)).astype(np.int32)
+    level_ptr = np.searchsorted(level[row_order], np.arange(levels + 1), side="left").astype(np.int32)
+    return levels, row_order, level_ptr
+
+
+def csr_trsv(row_ptr, col, vals, b, base=0, side=capi.TRSV_LOWER, diag=capi.TRSV_DIAG_STORED):
+    """x = T^-1 * b as include/spgpu/ext/trsv_device.h defines it, restated with the element type's own scalar arithmetic, one
+    operation at a time: acc = b_i; for each stored off-diagonal entry on `side` in storage order acc = acc - (a_ij * x_j), the
+    product rounded and then the difference; x_i = acc / a_ii, or acc under TRSV_DIAG_UNIT.  Complex goes through its real parts:
+    the product is re = ar*xr - ai*xi, im = ar*xi + ai*xr; the quotient den = dr*dr + di*di, re = (nr*dr + ni*di) / den,
+    im = (ni*dr - nr*di) / den.  Entries on the other side, and a diagonal under TRSV_DIAG_UNIT, are never read.  ValueError on what
+    spgpuCsrTrsvPlanDevice refuses.  One Python step per stored entry: a restatement for tests, not a tool."""
+    n_rows, ptr, col = _trsv_rows(row_ptr, col, base, side, diag)
+    vals, b = np.asarray(vals), np.asarray(b)
+    dtype = vals.dtype
+    if b.dtype != dtype:
+        raise ValueError("the matrix and b hold different types")
+    real = dtype.kind != "c"
+    part = dtype if real else np.dtype("f%d" % (dtype.itemsize // 2))
+    parts = 1 if real else 2
+    v = np.ascontiguousarray(vals).view(part).reshape(-1, parts)
+    x = np.ascontiguousarray(b[:n_rows]).copy().view(part).reshape(-1, parts)          # in place: b_i is read before x_i is written
+    lower, stored = side == capi.TRSV_LOWER, diag == capi.TRSV_DIAG_STORED
+    with np.errstate(all="ignore"):
+        for i in (range(n_rows) if lower else range(n_rows - 1, -1, -1)):
+            acc = [x[i, p] for p in range(parts)]
+            pivot = None
+            for e in range(ptr[i], ptr[i + 1]):
+                j = col[e]
+                if j == i:
+                    if stored:
+                        pivot = [v[e, p] for p in range(parts)]
+                elif (j < i) if lower else (j > i):
+                    if real:
+                        product = v[e, 0] * x[j, 0]
+                        acc = [acc[0] - product]
+                    else:
+                        ar, ai, xr, xi = v[e, 0], v[e, 1], x[j, 0], x[j, 1]
+                        rr, ii, ri, ir = ar * xr, ai * xi, ar * xi, ai * xr
+                        re, im = rr - ii, ri + ir
+                        acc = [acc[0] - re, acc[1] - im]
+            if stored and real:
+                acc = [acc[0] / pivot[0]]
+            elif stored:
+                (nr, ni), (dr, di) = acc, pivot
+                rr, ii = dr * dr, di * di
+                den = rr + ii
+                a, bb, c, d = nr * dr, ni * di, ni * dr, nr * di
+                top, bottom = a + bb, c - d
+                acc = [top / den, bottom / den]
+            for p in range(parts):
+                x[i, p] = acc[p]
+    return x.reshape(-1).view(dtype)
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
