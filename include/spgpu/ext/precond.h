@@ -14,7 +14,7 @@
  *
  * tools/pcg_amd.c runs that loop against the same iteration written with host scalars; INTEGRATION.md shows it in full.
  * A stronger preconditioner than the diagonal -- Gauss-Seidel, SSOR, the application of an ILU(0) -- is the sparse triangular
- * solve of ext/trsv_device.h.
+ * solve of ext/trsv_device.h; the ILU(0) factor itself comes from ext/ilu0_device.h.
  *
  * ARGUMENTS.  All arrays are device pointers.  The matrix arguments of a ?Diag call are the leading matrix arguments of the
  * matching SpMV (spgpu/hell.h, spgpu/ell.h, spgpu/hdia.h), in the same order and with the same meaning.  Only S and D are

@@ -5,11 +5,11 @@
  *
  * NEW: the whole of Gauss-Seidel and SSOR, as a smoother on the hierarchy that spgpu/ext/spgemm_device.h and
  * spgpu/ext/add_device.h build and as a preconditioner that is stronger than the diagonal of spgpu/ext/precond.h, and the
- * application half of every ILU(0) or IC(0), wherever the factor came from.  T is one triangle of a matrix A that is given WHOLE:
- * (D + L)^-1 and (D + U)^-1 come from A's own arrays, and an ILU(0) stored in A's pattern (unit L below, U on and above the
- * diagonal) is solved from one array with two plans.  The solve is an ANALYSIS of the dependencies, once
- * (spgpuCsrTrsvPlanDevice: the level of every row, the rows listed level by level), and a pass over the values at every
- * application (spgpuCsrTrsvDevice), which can sit in a captured graph.
+ * application half of every ILU(0) or IC(0), wherever the factor came from (ext/ilu0_device.h makes the ILU(0)).  T is one
+ * triangle of a matrix A that is given WHOLE: (D + L)^-1 and (D + U)^-1 come from A's own arrays, and an ILU(0) stored in A's
+ * pattern (unit L below, U on and above the diagonal) is solved from one array with two plans.  The solve is an ANALYSIS of the
+ * dependencies, once (spgpuCsrTrsvPlanDevice: the level of every row, the rows listed level by level), and a pass over the
+ * values at every application (spgpuCsrTrsvDevice), which can sit in a captured graph.
  *
  * All array arguments are DEVICE pointers unless marked host.  Every call runs on handle->currentStream.
  *

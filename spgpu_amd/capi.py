@@ -356,6 +356,27 @@ spgpuCsrTrsvDeviceWith = _bind("spgpuCsrTrsvDeviceWith", i32, spgpuCsrTrsvDevice
 TRSV_SOLVE_DEFAULT = _bind("spgpuCsrTrsvDefaultSolve", i32, [])()
 TRSV_CHAIN_WIDTH = _bind("spgpuCsrTrsvChainWidth", i32, [])()
 
+# ---- ext/ilu0_device.h: the incomplete factorisation ILU(0) on CSR arrays, level-scheduled, in HBM ------------------------------
+spgpuCsrIlu0WorkBytes = _decl("spgpuCsrIlu0WorkBytes", C.c_size_t, [i32])
+# (handle, &levelsCount, rowOrder, levelPtr, levelPtrHost (host, rows + 2 ints), diagPos, rows, rowPtr, colIndices, baseIndex, work)
+spgpuCsrIlu0PlanDevice = _decl("spgpuCsrIlu0PlanDevice", i32, [Handle, C.POINTER(i32), ptr, ptr, C.POINTER(i32), ptr, i32, ptr, ptr, i32, ptr])
+# (handle, luValues, aValues, rows, levelsCount, rowOrder, levelPtr, levelPtrHost (host), diagPos, rowPtr, colIndices, baseIndex, valuesType)
+spgpuCsrIlu0Device = _decl("spgpuCsrIlu0Device", i32, [Handle, ptr, ptr, i32, i32, ptr, ptr, C.POINTER(i32), ptr, ptr, ptr, i32, i32])
+# not in the headers: the row shapes and segmentings behind the call above, for the A/B tool and the tests that compare them
+# (..., shape, solve, maxBlocks): shape ILU0_SHAPE_THREAD (one thread per row), a power of two in [2, 64] (that many lanes of one
+# wavefront per row) or <= 0 for the public call's choice, csr_ilu0_default_shape(rows, nnz); solve TRSV_SOLVE_PLAIN (one launch per
+# level), TRSV_SOLVE_CHAINED (a run of levels of at most ILU0_CHAIN_WIDTH rows each is one launch of one workgroup) or < 0 for the
+# public call's choice; maxBlocks > 0 caps a level's grid
+ILU0_SHAPE_THREAD = 1
+spgpuCsrIlu0DeviceWith = _bind("spgpuCsrIlu0DeviceWith", i32, spgpuCsrIlu0Device.argtypes + [i32, i32, i32])
+csr_ilu0_default_shape = _bind("spgpuCsrIlu0DefaultShape", i32, [i32, i32])
+ILU0_SOLVE_DEFAULT = _bind("spgpuCsrIlu0DefaultSolve", i32, [])()
+ILU0_CHAIN_WIDTH = _bind("spgpuCsrIlu0ChainWidth", i32, [])()
+# the two GROUP widths the rule can choose, and the mean row lengths up to which THREAD and the narrow GROUP run
+ILU0_GROUP_NARROW, ILU0_GROUP_WIDE, ILU0_THREAD_MAX_MEAN, ILU0_NARROW_MAX_MEAN = (
+    _bind("spgpuCsrIlu0ShapeConstant", i32, [i32])(k) for k in range(4))
+ILU0_SHAPES = (ILU0_SHAPE_THREAD, ILU0_GROUP_NARROW, ILU0_GROUP_WIDE)
+
 
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])

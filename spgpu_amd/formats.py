@@ -436,6 +436,77 @@ def csr_trsv(row_ptr, col, vals, b, base=0, side=capi.TRSV_LOWER, diag=capi.TRSV
     return x.reshape(-1).view(dtype)
 
 
+def _ilu0_rows(row_ptr, col, base):
+    """The checks of spgpuCsrIlu0PlanDevice; (n_rows, 0-based row_ptr, 0-based col, diag_pos) as int64.  ValueError on each refusal."""
+    ptr = np.asarray(row_ptr, np.int64) - base
+    n_rows = ptr.size - 1
+    col = np.asarray(col, np.int64)[:ptr[-1]] - base
+    if col.size and (col.min() < 0 or col.max() >= n_rows):
+        raise ValueError("a column lies outside the matrix")
+    row_of = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(ptr))
+    if np.any(np.diff(row_of * max(n_rows, 1) + col) <= 0):      # rows never descend, so only a row's own order can fail
+        raise ValueError("a row does not ascend strictly")
+    at = np.flatnonzero(col == row_of)
+    if at.size != n_rows:                                         # ascending strictly: at most one per row
+        raise ValueError("a row stores no diagonal")
+    return n_rows, ptr, col, at
+
+
+def csr_ilu0_plan(row_ptr, col, base=0):
+    """The arrays include/spgpu/ext/ilu0_device.h defines, restated: (levels, row_order, level_ptr, diag_pos) of the square CSR
+    matrix in `base` -- csr_trsv_plan's for the lower triangle with a stored diagonal, and diag_pos[i], the 0-based position of entry
+    (i, i) in col.  ValueError on what spgpuCsrIlu0PlanDevice refuses: a column outside the matrix, a row that does not ascend
+    strictly, a missing diagonal."""
+    _, _, _, at = _ilu0_rows(row_ptr, col, base)
+    return csr_trsv_plan(row_ptr, col, base, capi.TRSV_LOWER, capi.TRSV_DIAG_STORED) + (at.astype(np.int32),)
+
+
+def csr_ilu0(row_ptr, col, vals, base=0):
+    """lu = ILU(0) of a as include/spgpu/ext/ilu0_device.h defines it, restated with the element type's own scalar arithmetic, one
+    operation at a time: lu starts as a copy of vals; row by row, for each stored (i, k) with k < i in ascending k first
+    lu_ik = lu_ik / lu_kk, then for each stored (k, j) with j > k in ascending j, where row i stores (i, j),
+    lu_ij = lu_ij - (lu_ik * lu_kj), the product rounded and then the difference; where it does not, the term is dropped.  Complex
+    goes through its real parts: the product is re = ar*xr - ai*xi, im = ar*xi + ai*xr; the quotient den = dr*dr + di*di,
+    re = (nr*dr + ni*di) / den, im = (ni*dr - nr*di) / den.  ValueError on what spgpuCsrIlu0PlanDevice refuses.  One Python step per
+    update: a restatement for tests, not a tool."""
+    n_rows, ptr, col, diag = _ilu0_rows(row_ptr, col, base)
+    vals = np.asarray(vals)
+    dtype = vals.dtype
+    real = dtype.kind != "c"
+    part = dtype if real else np.dtype("f%d" % (dtype.itemsize // 2))
+    parts = 1 if real else 2
+    lu = np.ascontiguousarray(vals[:ptr[-1]]).copy().view(part).reshape(-1, parts)
+    with np.errstate(all="ignore"):
+        for i in range(n_rows):
+            where = {int(col[q]): q for q in range(ptr[i], ptr[i + 1])}
+            for e in range(ptr[i], diag[i]):
+                k = col[e]
+                if real:
+                    m = [lu[e, 0] / lu[diag[k], 0]]
+                else:
+                    (nr, ni), (dr, di) = lu[e], lu[diag[k]]
+                    rr, ii = dr * dr, di * di
+                    den = rr + ii
+                    a, b, c, d = nr * dr, ni * di, ni * dr, nr * di
+                    top, bottom = a + b, c - d
+                    m = [top / den, bottom / den]
+                for p in range(parts):
+                    lu[e, p] = m[p]
+                for at in range(diag[k] + 1, ptr[k + 1]):
+                    q = where.get(int(col[at]))
+                    if q is None:
+                        continue                                   # no fill
+                    if real:
+                        product = m[0] * lu[at, 0]
+                        lu[q, 0] = lu[q, 0] - product
+                    else:
+                        (ar, ai), (xr, xi) = m, lu[at]
+                        rr, ii, ri, ir = ar * xr, ai * xi, ar * xi, ai * xr
+                        re, im = rr - ii, ri + ir
+                        lu[q, 0], lu[q, 1] = lu[q, 0] - re, lu[q, 1] - im
+    return lu.reshape(-1).view(dtype)
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
