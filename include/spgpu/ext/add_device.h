@@ -72,6 +72,7 @@
  *             spgpuCsrToHellValuesDevice(...);  spgpuDhellspmv(...);
  *
  * Solving with a triangle of the CSR matrix this builds -- a Gauss-Seidel sweep on M + dt * K -- is ext/trsv_device.h.
+ * The tentative prolongator T of P = T - omega * (A * T) comes out of ext/aggregate_device.h.
  */
 #include "../core.h"
 

@@ -71,6 +71,7 @@
  *
  * The sum of two CSR matrices -- the smoothed prolongator P = T - omega * (A * T) after this product -- is ext/add_device.h.
  * A Gauss-Seidel smoother for the hierarchy these products build is the triangular solve of ext/trsv_device.h.
+ * The tentative prolongator T itself -- strength of connection, aggregates, T in CSR -- comes out of ext/aggregate_device.h.
  */
 #include "../core.h"
 

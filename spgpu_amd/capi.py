@@ -377,6 +377,24 @@ ILU0_GROUP_NARROW, ILU0_GROUP_WIDE, ILU0_THREAD_MAX_MEAN, ILU0_NARROW_MAX_MEAN =
     _bind("spgpuCsrIlu0ShapeConstant", i32, [i32])(k) for k in range(4))
 ILU0_SHAPES = (ILU0_SHAPE_THREAD, ILU0_GROUP_NARROW, ILU0_GROUP_WIDE)
 
+# ---- ext/aggregate_device.h: strength of connection, MIS-2 aggregates and the tentative prolongator on CSR arrays, in HBM -----------
+spgpuCsrAggregateWorkBytes = _decl("spgpuCsrAggregateWorkBytes", C.c_size_t, [i32])
+# (handle, strong (bytes, one per entry), diagAbs, rows, rowPtr, colIndices, values, baseIndex, theta, valuesType)
+spgpuCsrStrengthDevice = _decl("spgpuCsrStrengthDevice", i32, [Handle, ptr, ptr, i32, ptr, ptr, ptr, i32, C.c_double, i32])
+# (handle, &aggregatesCount, &roundsCount, aggregateOf, aggregateSize, rows, rowPtr, colIndices, strong or NULL, baseIndex, work)
+spgpuCsrAggregateDevice = _decl("spgpuCsrAggregateDevice", i32, [Handle, C.POINTER(i32), C.POINTER(i32), ptr, ptr, i32, ptr, ptr, ptr, i32,
+                                                                ptr])
+# (handle, tRowPtr, tColIndices, tValues, rows, aggregateOf, candidate or NULL, baseIndex, valuesType)
+spgpuCsrTentativeDevice = _decl("spgpuCsrTentativeDevice", i32, [Handle, ptr, ptr, ptr, i32, ptr, ptr, i32, i32])
+# not in the headers: the row shapes behind the calls above, for the A/B tool and the tests that compare them
+# (..., shape, maxBlocks): shape AGG_SHAPE_THREAD (one thread per row), a power of two in [2, 64] (that many lanes of one wavefront
+# per row) or <= 0 for the public call's choice -- csr_aggregate_default_shape(rows, nnz) for the aggregation, one thread per row for
+# the strength call, which cannot read nnz without a synchronise; maxBlocks > 0 caps the grids
+AGG_SHAPE_THREAD = 1
+spgpuCsrAggregateDeviceWith = _bind("spgpuCsrAggregateDeviceWith", i32, spgpuCsrAggregateDevice.argtypes + [i32, i32])
+spgpuCsrStrengthDeviceWith = _bind("spgpuCsrStrengthDeviceWith", i32, spgpuCsrStrengthDevice.argtypes + [i32, i32])
+csr_aggregate_default_shape = _bind("spgpuCsrAggregateDefaultShape", i32, [i32, i32])
+
 
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])

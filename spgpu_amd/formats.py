@@ -507,6 +507,111 @@ def csr_ilu0(row_ptr, col, vals, base=0):
     return lu.reshape(-1).view(dtype)
 
 
+def _square_csr(row_ptr, col, base):
+    """(n_rows, 0-based row_ptr, 0-based col, the row of every entry) of a square CSR matrix in `base`, as int64."""
+    ptr = np.asarray(row_ptr, np.int64) - base
+    n_rows = ptr.size - 1
+    col = np.asarray(col, np.int64)[:ptr[-1]] - base
+    return n_rows, ptr, col, np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(ptr))
+
+
+def csr_strength(row_ptr, col, vals, base, theta):
+    """(strong, diag_abs) as include/spgpu/ext/aggregate_device.h defines them, restated in the element type's own arithmetic, one
+    operation at a time: d_i = |a_ii| of the first stored (i, i), +0 without one; t = T(theta*theta), the product in double and one
+    conversion; strong[p] = (j != i) and a_ij*a_ij >= (t*d_i)*d_j.  A NaN on either side gives 0; a column outside the matrix gives 0
+    and d_j is not read.  Real types only (ValueError otherwise)."""
+    n_rows, ptr, col, row_of = _square_csr(row_ptr, col, base)
+    vals = np.ascontiguousarray(np.asarray(vals)[:ptr[-1]])
+    if vals.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("the strength of connection is defined for real types only")
+    T = vals.dtype.type
+    diag_abs = np.zeros(n_rows, vals.dtype)
+    at = np.flatnonzero(col == row_of)
+    rows_with, first = np.unique(row_of[at], return_index=True)       # the first stored diagonal of every row that has one
+    diag_abs[rows_with] = np.abs(vals[at[first]])
+    t = T(float(theta) * float(theta))
+    inside = (col >= 0) & (col < n_rows)
+    other = np.where(inside, col, 0)
+    with np.errstate(all="ignore"):
+        lhs = vals * vals
+        rhs = (t * diag_abs[row_of]) * diag_abs[other]
+        strong = inside & (col != row_of) & (lhs >= rhs)
+    return strong.astype(np.uint8), diag_abs
+
+
+def _lowbias32(x):
+    x = np.asarray(x, np.uint32).copy()
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def aggregate_priority(n_rows):
+    """hash(i) = lowbias32(i) >> 1 for i < n_rows (uint64, 31 bits)."""
+    return (_lowbias32(np.arange(n_rows, dtype=np.uint32)) >> np.uint32(1)).astype(np.uint64)
+
+
+def csr_aggregate(row_ptr, col, strong, base, priority=None):
+    """(count, rounds, aggregate_of, sizes) as include/spgpu/ext/aggregate_device.h defines them, restated round by round.  S(i) is
+    the columns j != i of row i's entries with strong[p] != 0 (strong None: every stored j != i).  Every node starts UNDECIDED with
+    the tuple (state, hash(i), i) in one 64-bit word, OUT = 0 < UNDECIDED = 1 < ROOT = 2.  A round: t1[i] = max(t0[i], max of t0 over
+    S(i)), t2[i] = max(t1[i], max of t1 over S(i)); an undecided i with t2[i] == t0[i] becomes ROOT, otherwise under a ROOT's tuple
+    OUT.  Rounds repeat until nobody is undecided; roots are numbered by ascending row; two joining passes, each reading the array of
+    the pass before, give an unassigned node the smallest aggregate number among the assigned nodes of S(i).  ValueError on what
+    spgpuCsrAggregateDevice refuses: a neighbour outside the matrix.  `priority` replaces hash(i) (uint64 below 2**31): for tests
+    that compare priorities, not a parameter of the device call."""
+    n_rows, ptr, col, row_of = _square_csr(row_ptr, col, base)
+    keep = np.ones(col.size, bool) if strong is None else np.asarray(strong)[:col.size] != 0
+    if np.any(keep & ((col < 0) | (col >= n_rows))):
+        raise ValueError("a neighbour lies outside the matrix")
+    keep &= col != row_of
+    src, dst = row_of[keep], col[keep]
+    OUT, UNDECIDED, ROOT = np.uint64(0), np.uint64(1), np.uint64(2)
+    shift = np.uint64(62)
+    low = ((aggregate_priority(n_rows) if priority is None else np.asarray(priority, np.uint64)) << np.uint64(31)) \
+        | np.arange(n_rows, dtype=np.uint64)
+    state = np.full(n_rows, UNDECIDED, np.uint64)
+
+    def sweep(t):
+        out = t.copy()
+        np.maximum.at(out, src, t[dst])
+        return out
+
+    rounds = 0
+    while np.any(state == UNDECIDED):
+        t0 = (state << shift) | low
+        t2 = sweep(sweep(t0))
+        undecided = state == UNDECIDED
+        roots = undecided & (t2 == t0)
+        outs = undecided & ~roots & ((t2 >> shift) == ROOT)
+        state[roots], state[outs] = ROOT, OUT
+        rounds += 1
+    is_root = state == ROOT
+    count = int(is_root.sum())
+    number = np.cumsum(is_root) - is_root                             # the exclusive scan
+    assigned = np.where(is_root, number, -1).astype(np.int64)
+    for _ in range(2):                                                # the joining passes, each from the array of the pass before
+        theirs = assigned[dst]
+        best = np.full(n_rows, np.iinfo(np.int64).max, np.int64)
+        np.minimum.at(best, src[theirs >= 0], theirs[theirs >= 0])
+        assigned = np.where((assigned < 0) & (best < np.iinfo(np.int64).max), best, assigned)
+    assert n_rows == 0 or assigned.min() >= 0, "a node without an aggregate after pass 2"
+    return count, rounds, assigned.astype(np.int32), np.bincount(assigned, minlength=count).astype(np.int32)
+
+
+def csr_tentative(aggregate_of, candidate, base, dtype):
+    """(t_ptr, t_cols, t_vals) of the tentative prolongator of include/spgpu/ext/aggregate_device.h: one entry per row, in column
+    aggregate_of[i] + base, holding the bits of candidate[i], or 1 of `dtype` when candidate is None."""
+    aggregate_of = np.asarray(aggregate_of, np.int32)
+    n_rows = aggregate_of.size
+    vals = np.ones(n_rows, dtype) if candidate is None else np.ascontiguousarray(np.asarray(candidate)[:n_rows]).copy()
+    assert vals.dtype == np.dtype(dtype)
+    return (np.arange(n_rows + 1, dtype=np.int32) + np.int32(base)), aggregate_of + np.int32(base), vals
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
