@@ -16,7 +16,7 @@
  * of steps on a stencil, quadratic in the length of a long row).  If the bisection ends on an equal column, that position
  * supplies the b term.  An entry of B whose column A's row does not hold lands at cRowPtr[i] + (f - bRowPtr[i]) + below with the
  * roles exchanged; one that A holds is written by A's entry.  One writer per element, no atomics, and the same arithmetic
- * (addScale, addBoth: contraction off) in both fills, so both give the same bytes:
+ * (exactMul, exactScaledSum of csr_shared.hip.h: contraction off) in both fills, so both give the same bytes:
  *   plain    (csrAddEntryKernel) one thread per stored entry of A and of B, grid-strided; the counts come from the row pointers
  *            on the device; the row by bisection of the row pointer, the rank by bisection of the other row in global memory.
  *            No LDS;
@@ -31,7 +31,7 @@
  *            range of C in near-monotone order.  The row set aside is done by the plain method in the same launch, the
  *            workgroup striding over its entries: no host knowledge, no second launch.
  */
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -49,7 +49,6 @@ constexpr int kAddSlice = 4096;  /* ints of LDS per matrix: kAddTile - 1 + kAddR
 static_assert(kAddRowCap >= kAddTile, "a row that is not the last of its tile is shorter than the tile and must be staged");
 static_assert(kAddTile - 1 + kAddRowCap <= kAddSlice, "the staged rows' slices must fit");
 static_assert(2 * kAddSlice * sizeof(int) <= 64 * 1024, "static LDS within 64 KB");
-constexpr unsigned kAddMaxBlocks = 1048576;
 constexpr int kAddFillBlocks = 2048; /* enough workgroups of 256 to fill 256 CUs, where the host does not know C's size */
 
 enum { SPGPU_ADD_FILL_PLAIN = 0, SPGPU_ADD_FILL_STAGED = 1 };
@@ -105,60 +104,6 @@ __global__ __launch_bounds__(kCvThreads) void csrAddBaseKernel(int* rowPtr, long
         rowPtr[i] += base;
 }
 
-/* ---- the arithmetic of the contract ---- */
-/* s * v, rounded once; complex: four products, a difference and a sum, each rounded */
-__device__ inline float addScale(float s, float v)
-{
-#pragma clang fp contract(off)
-    return s * v;
-}
-__device__ inline double addScale(double s, double v)
-{
-#pragma clang fp contract(off)
-    return s * v;
-}
-template <typename R> __device__ inline Cx<R> addScale(Cx<R> s, Cx<R> v)
-{
-#pragma clang fp contract(off)
-    const R rr = s.x * v.x, ii = s.y * v.y, ri = s.x * v.y, ir = s.y * v.x;
-    const R re = rr - ii, im = ri + ir;
-    return Cx<R>{re, im};
-}
-/* (alpha * a) + (beta * b): the two products rounded, then the sum; the pragma keeps hipcc, which contracts by default, from
- * fusing a product into the sum */
-__device__ inline float addBoth(float alpha, float a, float beta, float b)
-{
-#pragma clang fp contract(off)
-    const float p = alpha * a, q = beta * b;
-    return p + q;
-}
-__device__ inline double addBoth(double alpha, double a, double beta, double b)
-{
-#pragma clang fp contract(off)
-    const double p = alpha * a, q = beta * b;
-    return p + q;
-}
-template <typename R> __device__ inline Cx<R> addBoth(Cx<R> alpha, Cx<R> a, Cx<R> beta, Cx<R> b)
-{
-#pragma clang fp contract(off)
-    const Cx<R> p = addScale(alpha, a), q = addScale(beta, b);
-    const R re = p.x + q.x, im = p.y + q.y;
-    return Cx<R>{re, im};
-}
-
-/* first position in [lo, hi) of `cols` whose column is >= j (hi if none) */
-__device__ inline int addLowerBound(const int* cols, int lo, int hi, int j)
-{
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (cols[mid] < j)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 /* how many columns own[ownFrom, ownTo) and other[otherFrom, otherTo) -- both ascending -- have in common: a walk over both */
 __device__ inline int addCommon(const int* own, int ownFrom, int ownTo, const int* other, int otherFrom, int otherTo)
 {
@@ -197,9 +142,9 @@ __device__ inline void addPlace(int* cIdx, T* cVal, int cStart, int offsetInRow,
     const long long at = (long long)cStart + offsetInRow + below;
     T c;
     if (OWN_IS_A && match)
-        c = addBoth(ownScalar, ownValue, otherScalar, otherVal[otherAt]);
+        c = exactScaledSum(ownScalar, ownValue, otherScalar, otherVal[otherAt]);
     else
-        c = addScale(ownScalar, ownValue);
+        c = exactMul(ownScalar, ownValue);
     cVal[at] = c;
     if (FULL)
         cIdx[at] = column;
@@ -212,7 +157,7 @@ __device__ inline void addEntryPlain(int* cIdx, T* cVal, int i, long long u, T o
 {
     const int column = ownIdx[u];
     const int o0 = otherPtr[i] - base, o1 = otherPtr[i + 1] - base;
-    const int lo = addLowerBound(otherIdx, o0, o1, column);
+    const int lo = lowerBound(otherIdx, o0, o1, column);
     const bool match = lo < o1 && otherIdx[lo] == column;
     if (!OWN_IS_A && match)
         return;
@@ -254,7 +199,7 @@ __device__ inline void addSliceStaged(int* cIdx, T* cVal, int r0, int rs, T ownS
         const int i = addRowOf(ownPtr, r0, rs, base, u);
         const int column = ownCols[x];
         const int o0 = otherPtr[i] - base - other0, o1 = otherPtr[i + 1] - base - other0;
-        const int lo = addLowerBound(otherCols, o0, o1, column);
+        const int lo = lowerBound(otherCols, o0, o1, column);
         const bool match = lo < o1 && otherCols[lo] == column;
         if (!OWN_IS_A && match)
             continue;
@@ -330,12 +275,6 @@ __global__ __launch_bounds__(kAddThreads) void csrAddTileKernel(int* cIdx, T* cV
     }
 }
 
-static unsigned addGridFor(long long blocks, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kAddMaxBlocks;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 /* entries < 0: the host does not know how many entries C has (the values-only calls) */
 template <typename T, bool FULL>
 static void launchCsrAdd(hipStream_t s, int* cIdx, void* cVal, int entries, int rows, const void* alpha, bool scalarsOnDevice, const int* aPtr,
@@ -358,13 +297,13 @@ static void launchCsrAdd(hipStream_t s, int* cIdx, void* cVal, int entries, int 
     if (fill == SPGPU_ADD_FILL_PLAIN) {
         /* A and B together hold at least as many entries as C and at most twice as many */
         const long long blocks = entries >= 0 ? (2 * (long long)entries + kAddThreads - 1) / kAddThreads : unknown;
-        hipLaunchKernelGGL((csrAddEntryKernel<T, FULL>), dim3(addGridFor(blocks, maxBlocks)), dim3(kAddThreads), 0, s, cIdx, static_cast<T*>(cVal),
+        hipLaunchKernelGGL((csrAddEntryKernel<T, FULL>), dim3(cappedGrid(blocks, 1, maxBlocks)), dim3(kAddThreads), 0, s, cIdx, static_cast<T*>(cVal),
                            rows, alphaValue, alphaAt, aPtr, aIdx, static_cast<const T*>(aVal), betaValue, betaAt, bPtr, bIdx,
                            static_cast<const T*>(bVal), cPtr, base);
         return;
     }
     const long long blocks = entries >= 0 ? ((long long)entries + kAddTile - 1) / kAddTile : unknown;
-    hipLaunchKernelGGL((csrAddTileKernel<T, FULL>), dim3(addGridFor(blocks, maxBlocks)), dim3(kAddThreads), 0, s, cIdx, static_cast<T*>(cVal), rows,
+    hipLaunchKernelGGL((csrAddTileKernel<T, FULL>), dim3(cappedGrid(blocks, 1, maxBlocks)), dim3(kAddThreads), 0, s, cIdx, static_cast<T*>(cVal), rows,
                        alphaValue, alphaAt, aPtr, aIdx, static_cast<const T*>(aVal), betaValue, betaAt, bPtr, bIdx, static_cast<const T*>(bVal),
                        cPtr, base);
 }
@@ -378,35 +317,20 @@ static spgpuStatus_t csrAdd(spgpuHandle_t handle, int* cIdx, void* cVal, int ent
         fill = kAddDefaultFill;
     if (fill != SPGPU_ADD_FILL_PLAIN && fill != SPGPU_ADD_FILL_STAGED)
         return SPGPU_UNSUPPORTED;
-    if (type != SPGPU_TYPE_FLOAT && type != SPGPU_TYPE_DOUBLE && type != SPGPU_TYPE_COMPLEX_FLOAT && type != SPGPU_TYPE_COMPLEX_DOUBLE)
-        return SPGPU_UNSUPPORTED;
     if (!alpha || !beta || !cVal)
         return SPGPU_UNSUPPORTED;
     hipStream_t s = handle->currentStream;
-#define SPGPU_ADD_LAUNCH(T)                                                                                                                      \
-    do {                                                                                                                                         \
-        if (cIdx)                                                                                                                                \
-            launchCsrAdd<T, true>(s, cIdx, cVal, entries, rows, alpha, scalarsOnDevice, aPtr, aIdx, aVal, beta, bPtr, bIdx, bVal, cPtr, base,   \
-                                  fill, maxBlocks);                                                                                              \
-        else                                                                                                                                     \
-            launchCsrAdd<T, false>(s, cIdx, cVal, entries, rows, alpha, scalarsOnDevice, aPtr, aIdx, aVal, beta, bPtr, bIdx, bVal, cPtr, base,  \
-                                   fill, maxBlocks);                                                                                             \
-    } while (0)
-    switch (type) {
-    case SPGPU_TYPE_FLOAT:
-        SPGPU_ADD_LAUNCH(float);
-        break;
-    case SPGPU_TYPE_DOUBLE:
-        SPGPU_ADD_LAUNCH(double);
-        break;
-    case SPGPU_TYPE_COMPLEX_FLOAT:
-        SPGPU_ADD_LAUNCH(cfloat);
-        break;
-    default:
-        SPGPU_ADD_LAUNCH(cdouble);
-        break;
-    }
-#undef SPGPU_ADD_LAUNCH
+    const bool launched = forValueType(type, [&](auto tag) {
+        using T = decltype(tag);
+        if (cIdx)
+            launchCsrAdd<T, true>(s, cIdx, cVal, entries, rows, alpha, scalarsOnDevice, aPtr, aIdx, aVal, beta, bPtr, bIdx, bVal, cPtr, base, fill,
+                                  maxBlocks);
+        else
+            launchCsrAdd<T, false>(s, cIdx, cVal, entries, rows, alpha, scalarsOnDevice, aPtr, aIdx, aVal, beta, bPtr, bIdx, bVal, cPtr, base, fill,
+                                   maxBlocks);
+    });
+    if (!launched)
+        return SPGPU_UNSUPPORTED;
     spgpuDebugCheck(handle, "csr add");
     return SPGPU_SUCCESS;
 }

@@ -26,7 +26,7 @@
  * After the rounds t1 holds the two arrays of the joining passes and t2 the two arrays of the sort.
  */
 #include "aggregate_rules.h"
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -328,15 +328,6 @@ static AggregateWork carveAggregate(void* work, int rows)
     return w;
 }
 
-/* smallest b with 2^b >= n (n >= 1) */
-static int aggBitsFor(long long n)
-{
-    int b = 0;
-    while (((long long)1 << b) < n)
-        ++b;
-    return b;
-}
-
 template <typename T>
 static void launchStrength(hipStream_t s, unsigned char* strong, void* diagAbs, int rows, const int* ptr, const int* idx, const void* values, int base,
                            double theta, int shape, int maxBlocks)
@@ -477,7 +468,7 @@ spgpuStatus_t spgpuCsrAggregateDeviceWith(spgpuHandle_t handle, int* aggregatesC
     /* ---- the sizes: aggregateOf sorted by a split per bit of the largest number, then two lower bounds per aggregate ---- */
     const int* sorted = aggregateOf;
     int* into = keysA;
-    const int bits = aggBitsFor(count);
+    const int bits = bitsFor(count);
     for (int bit = 0; bit < bits; ++bit) {
         hipLaunchKernelGGL(aggSplitFlagsKernel, rowGrid, dim3(kCvThreads), 0, s, w.a, sorted, rows, bit);
         exclusiveScan(s, w.b, w.a, rows, 1, w.totals);

@@ -26,8 +26,9 @@
  *            chunk keeps its running sum in the thread and goes on in the next chunk: a segment of any length is so many chunks.
  *            A tile whose segments all have length 1 (workgroup-uniform: its range is as long as the tile) is a straight gather.
  * Both start a sum from the first contribution and move a single contribution as it is.  No atomics, one writer per element.
+ * The head flags, the fill of an empty plan's row pointer, the key bits and the grid rule are those of csr_shared.hip.h / csr_host.h.
  */
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -43,7 +44,6 @@ constexpr int kAsmThreads = 256;
 constexpr int kAsmTile = kAsmThreads;                 /* matrix entries a workgroup owns: one per thread */
 constexpr int kAsmLoads = 4;                          /* gathers a thread issues together */
 constexpr int kAsmChunk = kAsmThreads * kAsmLoads;    /* positions of perm landed in LDS per trip */
-constexpr unsigned kAsmMaxBlocks = 1048576;
 
 enum { SPGPU_ASSEMBLE_FILL_PLAIN = 0, SPGPU_ASSEMBLE_FILL_STAGED = 1 };
 /* The fill the public calls run: the faster one on the element-by-element listing of a 3-D stencil pattern, 10 M rows, 5-6
@@ -95,15 +95,6 @@ static hipError_t asmSortTempBytes(size_t n, size_t* bytes)
     return err;
 }
 
-/* smallest b with 2^b >= n (n >= 1) */
-static int asmBitsFor(long long n)
-{
-    int b = 0;
-    while (((long long)1 << b) < n)
-        ++b;
-    return b;
-}
-
 /* ---- the plan ---- */
 __global__ __launch_bounds__(kCvThreads) void asmEmitKeysKernel(AsmKey* keys, int* ids, int* misc, int rows, int cols, int nnz,
                                                                 const int* cooRows, const int* cooCols, int cooBase, int colBits)
@@ -117,13 +108,6 @@ __global__ __launch_bounds__(kCvThreads) void asmEmitKeysKernel(AsmKey* keys, in
         keys[i] = bad ? (AsmKey)0 : ((AsmKey)r << colBits) | c;
         ids[i] = (int)i;
     }
-}
-
-__global__ __launch_bounds__(kCvThreads) void asmHeadFlagsKernel(int* flags, const AsmKey* keys, int nnz)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long p = (long long)blockIdx.x * kCvThreads + threadIdx.x; p < nnz; p += stride)
-        flags[p] = p == 0 || keys[p] != keys[p - 1];
 }
 
 /* a head at sorted position p is the first contribution of entry entryOf[p]; *unique = the number of heads */
@@ -147,13 +131,6 @@ __global__ __launch_bounds__(kCvThreads) void asmRowPtrKernel(int* csrRowPtr, co
         const int at = rowStart[r];
         csrRowPtr[r] = csrBase + (at < nnz ? entryOf[at] : *unique);
     }
-}
-
-__global__ __launch_bounds__(kCvThreads) void asmSetIntsKernel(int* out, long long n, int value)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long i = (long long)blockIdx.x * kCvThreads + threadIdx.x; i < n; i += stride)
-        out[i] = value;
 }
 
 /* ---- the fills ---- */
@@ -232,23 +209,16 @@ __global__ __launch_bounds__(kAsmThreads) void assembleStagedKernel(T* csrVals, 
     }
 }
 
-static unsigned asmGridFor(long long items, int perBlock, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kAsmMaxBlocks;
-    const long long blocks = (items + perBlock - 1) / perBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 template <typename T>
 static void launchValues(hipStream_t s, void* csrVals, int unique, const void* cooVals, const int* perm, const int* segPtr, int fill, int maxBlocks)
 {
     if (fill == SPGPU_ASSEMBLE_FILL_PLAIN) {
-        hipLaunchKernelGGL(assembleEntryKernel<T>, dim3(asmGridFor(unique, kAsmThreads, maxBlocks)), dim3(kAsmThreads), 0, s,
+        hipLaunchKernelGGL(assembleEntryKernel<T>, dim3(cappedGrid(unique, kAsmThreads, maxBlocks)), dim3(kAsmThreads), 0, s,
                            static_cast<T*>(csrVals), unique, static_cast<const T*>(cooVals), perm, segPtr);
         return;
     }
     const long long tiles = ((long long)unique + kAsmTile - 1) / kAsmTile;
-    hipLaunchKernelGGL(assembleStagedKernel<T>, dim3(asmGridFor(tiles, 1, maxBlocks)), dim3(kAsmThreads), 0, s, static_cast<T*>(csrVals), unique,
+    hipLaunchKernelGGL(assembleStagedKernel<T>, dim3(cappedGrid(tiles, 1, maxBlocks)), dim3(kAsmThreads), 0, s, static_cast<T*>(csrVals), unique,
                        tiles, static_cast<const T*>(cooVals), perm, segPtr);
 }
 
@@ -262,26 +232,15 @@ static spgpuStatus_t assemble(spgpuHandle_t handle, int* csrCols, void* csrVals,
         fill = kAsmDefaultFill;
     if (fill != SPGPU_ASSEMBLE_FILL_PLAIN && fill != SPGPU_ASSEMBLE_FILL_STAGED)
         return SPGPU_UNSUPPORTED;
-    if (type != SPGPU_TYPE_FLOAT && type != SPGPU_TYPE_DOUBLE && type != SPGPU_TYPE_COMPLEX_FLOAT && type != SPGPU_TYPE_COMPLEX_DOUBLE)
-        return SPGPU_UNSUPPORTED;
     hipStream_t s = handle->currentStream;
-    if (csrCols)
-        hipLaunchKernelGGL(asmColumnsKernel, dim3(asmGridFor(unique, kAsmThreads, maxBlocks)), dim3(kAsmThreads), 0, s, csrCols, unique, cooCols,
-                           csrBase - cooBase, perm, segPtr);
-    switch (type) {
-    case SPGPU_TYPE_FLOAT:
-        launchValues<float>(s, csrVals, unique, cooVals, perm, segPtr, fill, maxBlocks);
-        break;
-    case SPGPU_TYPE_DOUBLE:
-        launchValues<double>(s, csrVals, unique, cooVals, perm, segPtr, fill, maxBlocks);
-        break;
-    case SPGPU_TYPE_COMPLEX_FLOAT:
-        launchValues<cfloat>(s, csrVals, unique, cooVals, perm, segPtr, fill, maxBlocks);
-        break;
-    default:
-        launchValues<cdouble>(s, csrVals, unique, cooVals, perm, segPtr, fill, maxBlocks);
-        break;
-    }
+    const bool launched = forValueType(type, [&](auto tag) {
+        if (csrCols)
+            hipLaunchKernelGGL(asmColumnsKernel, dim3(cappedGrid(unique, kAsmThreads, maxBlocks)), dim3(kAsmThreads), 0, s, csrCols, unique,
+                               cooCols, csrBase - cooBase, perm, segPtr);
+        launchValues<decltype(tag)>(s, csrVals, unique, cooVals, perm, segPtr, fill, maxBlocks);
+    });
+    if (!launched)
+        return SPGPU_UNSUPPORTED;
     spgpuDebugCheck(handle, "coo assemble");
     return SPGPU_SUCCESS;
 }
@@ -327,7 +286,7 @@ spgpuStatus_t spgpuCooAssemblePlanDevice(spgpuHandle_t handle, int* uniqueCount,
         return SPGPU_SUCCESS;
     hipStream_t s = handle->currentStream;
     if (nonZerosCount <= 0) {
-        hipLaunchKernelGGL(asmSetIntsKernel, dim3(gridFor((long long)rowsCount + 1)), dim3(kCvThreads), 0, s, csrRowPtr, (long long)rowsCount + 1,
+        hipLaunchKernelGGL(csrSetIntsKernel, dim3(gridFor((long long)rowsCount + 1)), dim3(kCvThreads), 0, s, csrRowPtr, (long long)rowsCount + 1,
                            csrBaseIndex);
         (void)hipMemsetAsync(segPtr, 0, sizeof(int), s);
         spgpuDebugCheck(handle, "coo assemble plan");
@@ -337,7 +296,7 @@ spgpuStatus_t spgpuCooAssemblePlanDevice(spgpuHandle_t handle, int* uniqueCount,
         return SPGPU_UNSUPPORTED;
     const int nnz = nonZerosCount;
     const AssembleWork w = carveAssemble(work, rowsCount, (size_t)nnz);
-    const int rowBits = asmBitsFor(rowsCount), colBits = asmBitsFor(columnsCount);
+    const int rowBits = bitsFor(rowsCount), colBits = bitsFor(columnsCount);
     const size_t tiles = scanBlocks(nnz);
     const int* unique = w.totals + tiles; /* the scan's grand total */
     int* host = static_cast<int*>(spgpuPrivate(handle)->reduceHost);
@@ -351,7 +310,7 @@ spgpuStatus_t spgpuCooAssemblePlanDevice(spgpuHandle_t handle, int* uniqueCount,
     if (rocprim::radix_sort_pairs(w.temp, bytes, (const AsmKey*)w.keysA, w.keysB, (const int*)w.idA, perm, (size_t)nnz, 0u,
                                   (unsigned)(rowBits + colBits > 0 ? rowBits + colBits : 1), s) != hipSuccess)
         return SPGPU_UNSPECIFIED;
-    hipLaunchKernelGGL(asmHeadFlagsKernel, dim3(gridFor(nnz)), dim3(kCvThreads), 0, s, w.entryOf, (const AsmKey*)w.keysB, nnz);
+    hipLaunchKernelGGL(csrHeadFlagsKernel, dim3(gridFor(nnz)), dim3(kCvThreads), 0, s, w.entryOf, (const AsmKey*)w.keysB, nnz);
     exclusiveScan(s, w.entryOf, w.entryOf, (long long)nnz, 1, w.totals); /* in place: a thread reads its four flags before it writes them */
     hipLaunchKernelGGL(asmSegPtrKernel, dim3(gridFor(nnz)), dim3(kCvThreads), 0, s, segPtr, (const int*)w.entryOf, (const AsmKey*)w.keysB, nnz,
                        unique);

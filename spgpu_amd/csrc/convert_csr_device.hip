@@ -22,6 +22,7 @@
  * Lengths come from csrRowPtr.  No atomics, each slot has one writer: the arrays do not depend on scheduling.  A wavefront's
  * tile is its own; its LDS operations execute in order, the wave barriers only keep the compiler from moving them.
  */
+#include "csr_host.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -38,7 +39,6 @@ constexpr int kCsrReadPasses = kCsrGroupRows * kCsrChunk / kWave;   /* 8: 4 rows
 constexpr int kCsrWriteSteps = kCsrGroupRows * kCsrChunk / kWave;   /* 8: 2 columns x 32 rows per step */
 constexpr int kCsrRowsPerPass = kWave / kCsrChunk;                  /* 4 */
 constexpr int kCsrColsPerStep = kWave / kCsrGroupRows;              /* 2 */
-constexpr unsigned kCsrMaxBlocks = 1048576;                         /* as gridFor of the COO route */
 
 enum { SPGPU_CSR_FILL_PLAIN = 0, SPGPU_CSR_FILL_TRANSPOSE = 1 };
 constexpr int kCsrDefaultFill = SPGPU_CSR_FILL_TRANSPOSE;
@@ -188,19 +188,12 @@ __global__ __launch_bounds__(kCsrThreads) void csrRowLengthsKernel(int* rowLengt
     }
 }
 
-static unsigned csrGridFor(long long items, int perBlock, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kCsrMaxBlocks;
-    const long long blocks = (items + perBlock - 1) / perBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 template <typename ELEM, bool TO_HELL>
 static void launchCsrFill(hipStream_t s, void* values, int* indices, const CsrSlabs& slabs, int outBase, int rows, const int* rowPtr,
                           const int* csrCols, const void* csrVals, int csrBase, const int* rIdx, int fill, int maxBlocks)
 {
     if (fill == SPGPU_CSR_FILL_PLAIN) {
-        hipLaunchKernelGGL((csrRowFillKernel<ELEM, TO_HELL>), dim3(csrGridFor(rows, kCsrThreads, maxBlocks)), dim3(kCsrThreads), 0, s,
+        hipLaunchKernelGGL((csrRowFillKernel<ELEM, TO_HELL>), dim3(cappedGrid(rows, kCsrThreads, maxBlocks)), dim3(kCsrThreads), 0, s,
                            static_cast<ELEM*>(values), indices, slabs, outBase, rows, rowPtr, csrCols, static_cast<const ELEM*>(csrVals),
                            csrBase, rIdx);
         return;
@@ -208,7 +201,7 @@ static void launchCsrFill(hipStream_t s, void* values, int* indices, const CsrSl
     const int subsPerHack = TO_HELL ? (slabs.hackSize + kCsrGroupRows - 1) / kCsrGroupRows : 1;
     const long long hacks = TO_HELL ? ((long long)rows + slabs.hackSize - 1) / slabs.hackSize : ((long long)rows + kCsrGroupRows - 1) / kCsrGroupRows;
     const long long groups = hacks * subsPerHack;
-    hipLaunchKernelGGL((csrTransposeFillKernel<ELEM, TO_HELL>), dim3(csrGridFor(groups, kCsrWaves, maxBlocks)), dim3(kCsrThreads), 0, s,
+    hipLaunchKernelGGL((csrTransposeFillKernel<ELEM, TO_HELL>), dim3(cappedGrid(groups, kCsrWaves, maxBlocks)), dim3(kCsrThreads), 0, s,
                        static_cast<ELEM*>(values), indices, slabs, subsPerHack, groups, outBase, rows, rowPtr, csrCols,
                        static_cast<const ELEM*>(csrVals), csrBase, rIdx);
 }
@@ -281,7 +274,7 @@ spgpuStatus_t spgpuCsrRowLengthsDevice(spgpuHandle_t handle, int* rowLengths, in
     int* misc = static_cast<int*>(spgpuPrivate(handle)->reduceScratch);
     int* host = static_cast<int*>(spgpuPrivate(handle)->reduceHost);
     (void)hipMemsetAsync(misc, 0, 2 * sizeof(int), s);
-    hipLaunchKernelGGL(csrRowLengthsKernel, dim3(csrGridFor(rowsCount, kCsrThreads, 4096)), dim3(kCsrThreads), 0, s, rowLengths, rowsCount,
+    hipLaunchKernelGGL(csrRowLengthsKernel, dim3(cappedGrid(rowsCount, kCsrThreads, 4096)), dim3(kCsrThreads), 0, s, rowLengths, rowsCount,
                        csrRowPtr, csrBaseIndex, misc);
     (void)hipMemcpyAsync(host, misc, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
     (void)hipStreamSynchronize(s);

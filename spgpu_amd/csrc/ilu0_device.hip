@@ -26,9 +26,9 @@
  *   GROUP    L lanes of one wavefront own the row, lane l the positions = l (mod L).  The loop over k is uniform across the group;
  *            each lane bisects row k's upper part for the columns of its own entries beyond k.
  * Each entry's updates come in ascending k because its owner walks k in ascending order, and a k touches it at most once because
- * row k's columns are distinct.
+ * row k's columns are distinct.  The arithmetic is the triangular solve's: exactDiv and exactSubMul of csr_shared.hip.h.
  */
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "ilu0_rules.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
@@ -73,51 +73,6 @@ __global__ __launch_bounds__(kCvThreads) void ilu0CheckKernel(int* diagPos, int*
     }
 }
 
-/* ---- the arithmetic of the contract, restated from trsv_device.hip ---- */
-/* acc - (a * x): the product rounded, then the difference; the pragma keeps hipcc, which contracts by default, from fusing them */
-__device__ inline float ilu0SubMul(float acc, float a, float x)
-{
-#pragma clang fp contract(off)
-    const float p = a * x;
-    return acc - p;
-}
-__device__ inline double ilu0SubMul(double acc, double a, double x)
-{
-#pragma clang fp contract(off)
-    const double p = a * x;
-    return acc - p;
-}
-template <typename R> __device__ inline Cx<R> ilu0SubMul(Cx<R> acc, Cx<R> a, Cx<R> x)
-{
-#pragma clang fp contract(off)
-    const R rr = a.x * x.x, ii = a.y * x.y, ri = a.x * x.y, ir = a.y * x.x;
-    const R re = rr - ii, im = ri + ir;
-    const R outRe = acc.x - re, outIm = acc.y - im;
-    return Cx<R>{outRe, outIm};
-}
-/* n / d: one correctly rounded division (hipcc's default for fp32 too: no fast-math flag is passed) */
-__device__ inline float ilu0Div(float n, float d)
-{
-#pragma clang fp contract(off)
-    return n / d;
-}
-__device__ inline double ilu0Div(double n, double d)
-{
-#pragma clang fp contract(off)
-    return n / d;
-}
-/* the textbook quotient, every operation rounded separately; den may overflow or underflow (the header says so) */
-template <typename R> __device__ inline Cx<R> ilu0Div(Cx<R> n, Cx<R> d)
-{
-#pragma clang fp contract(off)
-    const R rr = d.x * d.x, ii = d.y * d.y;
-    const R den = rr + ii;
-    const R a = n.x * d.x, b = n.y * d.y, c = n.y * d.x, e = n.x * d.y;
-    const R top = a + b, bottom = c - e;
-    const R re = top / den, im = bottom / den;
-    return Cx<R>{re, im};
-}
-
 /* the value of lane `from` of this wavefront; every lane of the group that holds `from` is active at the call */
 __device__ inline float ilu0FromLane(float v, int from) { return __shfl(v, from, kWave); }
 __device__ inline double ilu0FromLane(double v, int from) { return __shfl(v, from, kWave); }
@@ -138,13 +93,13 @@ __device__ inline void ilu0RowThread(T* lu, const T* a, int i, const int* ptr, c
     for (int e = s; e < d; ++e) {
         const int k = idx[e] - base;
         const int dk = diagPos[k], endK = ptr[k + 1] - base;
-        const T m = ilu0Div(lu[e], lu[dk]);
+        const T m = exactDiv(lu[e], lu[dk]);
         lu[e] = m;
         int p = dk + 1, q = e + 1;
         while (p < endK && q < e1) {
             const int cp = idx[p], cq = idx[q];
             if (cp == cq) {
-                lu[q] = ilu0SubMul(lu[q], m, lu[p]);
+                lu[q] = exactSubMul(lu[q], m, lu[p]);
                 ++p;
                 ++q;
             } else if (cp < cq) {
@@ -172,7 +127,7 @@ __device__ inline void ilu0RowGroup(T* lu, const T* a, int i, const int* ptr, co
         const int owner = (e - s) & (L - 1);
         T m = zeroOf<T>();
         if (lane == owner) {
-            m = ilu0Div(lu[e], lu[dk]);
+            m = exactDiv(lu[e], lu[dk]);
             lu[e] = m;
         }
         m = ilu0FromLane(m, first + owner);
@@ -188,7 +143,7 @@ __device__ inline void ilu0RowGroup(T* lu, const T* a, int i, const int* ptr, co
                     hi = mid;
             }
             if (lo < endK && idx[lo] == c)
-                lu[q] = ilu0SubMul(lu[q], m, lu[lo]);
+                lu[q] = exactSubMul(lu[q], m, lu[lo]);
         }
     }
 }
@@ -337,9 +292,6 @@ spgpuStatus_t spgpuCsrIlu0DeviceWith(spgpuHandle_t handle, void* luValues, const
         solve = kIlu0DefaultSolve;
     if (solve != SPGPU_TRSV_SOLVE_PLAIN && solve != SPGPU_TRSV_SOLVE_CHAINED)
         return SPGPU_UNSUPPORTED;
-    if (valuesType != SPGPU_TYPE_FLOAT && valuesType != SPGPU_TYPE_DOUBLE && valuesType != SPGPU_TYPE_COMPLEX_FLOAT &&
-        valuesType != SPGPU_TYPE_COMPLEX_DOUBLE)
-        return SPGPU_UNSUPPORTED;
     if (!luValues || !aValues || !levelPtrHost)
         return SPGPU_UNSUPPORTED;
     if (shape <= 0)
@@ -347,23 +299,12 @@ spgpuStatus_t spgpuCsrIlu0DeviceWith(spgpuHandle_t handle, void* luValues, const
     if (!ilu0ShapeKnown(shape))
         return SPGPU_UNSUPPORTED;
     hipStream_t s = handle->currentStream;
-#define SPGPU_ILU0_LAUNCH(T) \
-    launchCsrIlu0<T>(s, luValues, aValues, levelsCount, rowOrder, levelPtr, levelPtrHost, diagPos, rowPtr, colIndices, baseIndex, shape, solve, maxBlocks)
-    switch (valuesType) {
-    case SPGPU_TYPE_FLOAT:
-        SPGPU_ILU0_LAUNCH(float);
-        break;
-    case SPGPU_TYPE_DOUBLE:
-        SPGPU_ILU0_LAUNCH(double);
-        break;
-    case SPGPU_TYPE_COMPLEX_FLOAT:
-        SPGPU_ILU0_LAUNCH(cfloat);
-        break;
-    default:
-        SPGPU_ILU0_LAUNCH(cdouble);
-        break;
-    }
-#undef SPGPU_ILU0_LAUNCH
+    const bool launched = forValueType(valuesType, [&](auto tag) {
+        launchCsrIlu0<decltype(tag)>(s, luValues, aValues, levelsCount, rowOrder, levelPtr, levelPtrHost, diagPos, rowPtr, colIndices, baseIndex,
+                                     shape, solve, maxBlocks);
+    });
+    if (!launched)
+        return SPGPU_UNSUPPORTED;
     spgpuDebugCheck(handle, "csr ilu0");
     return SPGPU_SUCCESS;
 }

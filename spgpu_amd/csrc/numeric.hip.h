@@ -17,14 +17,10 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
+#include "cx.h" /* Cx<R>, cfloat, cdouble */
 namespace spgpu {
 
 constexpr int kWave = 64;
-
-template <typename R> struct Cx { R x, y; };
-using cfloat = Cx<float>;
-using cdouble = Cx<double>;
 
 /* ---- zero / tests ------------------------------------------------------- */
 template <typename T> __device__ __host__ inline T zeroOf();

@@ -3,8 +3,8 @@
  * analysis lists every product a(i,k) * b(k,j) once, sorts the list and keeps the distinct (i, j); the fills add the products up
  * in the storage order of A's row.
  *
- * THE ANALYSIS is set-up code, on the machinery of the assembly (assemble_device.hip), restated here so that that file's object
- * code stays as it is.  Scratch layout (ints), S = productsCount rounded up to 64:
+ * THE ANALYSIS is set-up code, on the machinery of the assembly (assemble_device.hip); what the two share lies in
+ * csr_shared.hip.h and csr_host.h.  Scratch layout (ints), S = productsCount rounded up to 64:
  *   head    misc[16] | rowProducts[aRows+1] | rowStart[aRows+1] | rowTotals[tiles(aRows+1)+2], rounded up to 64 ints: a function
  *           of aRows alone, which is all spgpuCsrSpgemmProductsDevice touches.  misc[1] bad-input flag, misc[2..3] the number of
  *           products in 64 bits
@@ -20,7 +20,7 @@
  * is summed in 64 bits beside the int scan, and no kernel writes a key at or beyond productsCount: a caller's count that is not
  * the matrices', or a scan that wrapped, is reported after the synchronise and has written nothing out of bounds.
  *
- * THE FILLS add in the contract's order, each product rounded and then each sum (spgMulAdd: contraction off), and give the same
+ * THE FILLS add in the contract's order, each product rounded and then each sum (exactMulAdd of csr_shared.hip.h: contraction off), and give the same
  * bytes:
  *   plain    (spgemmEntryKernel) one thread per entry u of C: its row by bisection of cRowPtr, then a walk over A's row in storage
  *            order with a bisection of B's row k for column j per step.  No LDS;
@@ -33,7 +33,7 @@
  *            entries.  LDS per workgroup: kSpgWaves * kSpgRowCap * (4 + sizeof(T)) bytes, 40 KB for the 16-byte type.
  * No atomics, one writer per element.
  */
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -50,7 +50,6 @@ typedef unsigned long long SpgKey;
 constexpr int kSpgThreads = 256;
 constexpr int kSpgWaves = kSpgThreads / kWave;
 constexpr int kSpgRowCap = 512; /* entries of a row of C that a wavefront keeps in LDS: 4 * 512 * (4 + 16) = 40 KB at most */
-constexpr unsigned kSpgMaxBlocks = 1048576;
 constexpr int kSpgFillBlocks = 2048; /* enough workgroups of 256 to fill 256 CUs, where the host does not know C's size */
 
 enum { SPGPU_SPGEMM_FILL_PLAIN = 0, SPGPU_SPGEMM_FILL_STAGED = 1 };
@@ -106,15 +105,6 @@ static hipError_t spgSortTempBytes(size_t n, size_t* bytes)
     const hipError_t err = rocprim::radix_sort_keys(nullptr, need, (const SpgKey*)nullptr, (SpgKey*)nullptr, n);
     *bytes = alignUpCv(need, 256);
     return err;
-}
-
-/* smallest b with 2^b >= n (n >= 1) */
-static int spgBitsFor(long long n)
-{
-    int b = 0;
-    while (((long long)1 << b) < n)
-        ++b;
-    return b;
 }
 
 /* ---- the analysis ---- */
@@ -174,13 +164,6 @@ __global__ __launch_bounds__(kCvThreads) void spgExpandKernel(SpgKey* keys, int*
     }
 }
 
-__global__ __launch_bounds__(kCvThreads) void spgHeadFlagsKernel(int* flags, const SpgKey* keys, int n)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long p = (long long)blockIdx.x * kCvThreads + threadIdx.x; p < n; p += stride)
-        flags[p] = p == 0 || keys[p] != keys[p - 1];
-}
-
 /* a head at sorted position p is entry entryOf[p] of C: its column is the key's low bits */
 __global__ __launch_bounds__(kCvThreads) void spgColumnsKernel(int* cCols, const int* entryOf, const SpgKey* keys, int n, SpgKey colMask, int base)
 {
@@ -201,36 +184,7 @@ __global__ __launch_bounds__(kCvThreads) void spgRowPtrKernel(int* cRowPtr, cons
     }
 }
 
-__global__ __launch_bounds__(kCvThreads) void spgSetIntsKernel(int* out, long long n, int value)
-{
-    const long long stride = (long long)gridDim.x * kCvThreads;
-    for (long long i = (long long)blockIdx.x * kCvThreads + threadIdx.x; i < n; i += stride)
-        out[i] = value;
-}
-
 /* ---- the fills ---- */
-/* s + a * b, the product rounded, then the sum: the pragma keeps hipcc, which contracts by default, from fusing the two. */
-__device__ inline float spgMulAdd(float s, float a, float b)
-{
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return s + p;
-}
-__device__ inline double spgMulAdd(double s, double a, double b)
-{
-#pragma clang fp contract(off)
-    const double p = a * b;
-    return s + p;
-}
-/* re = ar*br - ai*bi, im = ar*bi + ai*br: four products, a difference and a sum, each rounded, then the two sums */
-template <typename R> __device__ inline Cx<R> spgMulAdd(Cx<R> s, Cx<R> a, Cx<R> b)
-{
-#pragma clang fp contract(off)
-    const R rr = a.x * b.x, ii = a.y * b.y, ri = a.x * b.y, ir = a.y * b.x;
-    const R re = rr - ii, im = ri + ir;
-    return Cx<R>{s.x + re, s.y + im};
-}
-
 /* c(i, j) by the plain method: A's row in storage order, B's row k bisected for column j (columns compared in the common base) */
 template <typename T>
 __device__ inline T spgEntry(int i, int j, const int* aPtr, const int* aIdx, const T* aVal, const int* bPtr, const int* bIdx, const T* bVal,
@@ -250,7 +204,7 @@ __device__ inline T spgEntry(int i, int j, const int* aPtr, const int* aIdx, con
                 hi = mid;
         }
         if (lo < end && bIdx[lo] == j)
-            sum = spgMulAdd(sum, aVal[e], bVal[lo]);
+            sum = exactMulAdd(sum, aVal[e], bVal[lo]);
     }
     return sum;
 }
@@ -334,7 +288,7 @@ __global__ __launch_bounds__(kSpgThreads) void spgemmRowKernel(T* cVal, int aRow
                         hi = mid;
                 }
                 if (lo < len && cols[lo] == j) /* always, for the pattern the plan made */
-                    vals[lo] = spgMulAdd(vals[lo], a, b);
+                    vals[lo] = exactMulAdd(vals[lo], a, b);
             }
             spgWaveSync(); /* this round's slot writes before the next round's slot reads: another lane may hold the slot then */
         }
@@ -342,13 +296,6 @@ __global__ __launch_bounds__(kSpgThreads) void spgemmRowKernel(T* cVal, int aRow
             cVal[c0 + t] = vals[t];
         spgWaveSync(); /* the next row zeroes what this one read */
     }
-}
-
-static unsigned spgGridFor(long long items, int perBlock, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kSpgMaxBlocks;
-    const long long blocks = (items + perBlock - 1) / perBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
 
 /* entries < 0: the host does not know how many entries C has (the values-only call) */
@@ -360,11 +307,11 @@ static void launchSpgemm(hipStream_t s, void* cVal, int entries, int aRows, cons
         long long blocks = entries >= 0 ? ((long long)entries + kSpgThreads - 1) / kSpgThreads : ((long long)aRows + 15) / 16;
         if (entries < 0 && blocks < kSpgFillBlocks)
             blocks = kSpgFillBlocks;
-        hipLaunchKernelGGL(spgemmEntryKernel<T>, dim3(spgGridFor(blocks, 1, maxBlocks)), dim3(kSpgThreads), 0, s, static_cast<T*>(cVal), aRows, aPtr,
+        hipLaunchKernelGGL(spgemmEntryKernel<T>, dim3(cappedGrid(blocks, 1, maxBlocks)), dim3(kSpgThreads), 0, s, static_cast<T*>(cVal), aRows, aPtr,
                            aIdx, static_cast<const T*>(aVal), bPtr, bIdx, static_cast<const T*>(bVal), cPtr, cIdx, base);
         return;
     }
-    hipLaunchKernelGGL(spgemmRowKernel<T>, dim3(spgGridFor(aRows, kSpgWaves, maxBlocks)), dim3(kSpgThreads), 0, s, static_cast<T*>(cVal), aRows,
+    hipLaunchKernelGGL(spgemmRowKernel<T>, dim3(cappedGrid(aRows, kSpgWaves, maxBlocks)), dim3(kSpgThreads), 0, s, static_cast<T*>(cVal), aRows,
                        aPtr, aIdx, static_cast<const T*>(aVal), bPtr, bIdx, static_cast<const T*>(bVal), cPtr, cIdx, base);
 }
 
@@ -380,29 +327,18 @@ static spgpuStatus_t spgemm(spgpuHandle_t handle, int* cCols, void* cVal, int en
         fill = kSpgDefaultFill;
     if (fill != SPGPU_SPGEMM_FILL_PLAIN && fill != SPGPU_SPGEMM_FILL_STAGED)
         return SPGPU_UNSUPPORTED;
-    if (type != SPGPU_TYPE_FLOAT && type != SPGPU_TYPE_DOUBLE && type != SPGPU_TYPE_COMPLEX_FLOAT && type != SPGPU_TYPE_COMPLEX_DOUBLE)
-        return SPGPU_UNSUPPORTED;
     if (!cCols || (entries > 0 && !work))
         return SPGPU_UNSUPPORTED;
     hipStream_t s = handle->currentStream;
-    if (entries > 0) {
-        const SpgemmWork w = carveSpgemm(const_cast<void*>(work), aRows, 0); /* the columns' place depends on aRows alone */
-        (void)hipMemcpyAsync(cCols, w.cCols, (size_t)entries * sizeof(int), hipMemcpyDeviceToDevice, s);
-    }
-    switch (type) {
-    case SPGPU_TYPE_FLOAT:
-        launchSpgemm<float>(s, cVal, entries, aRows, aPtr, aIdx, aVal, bPtr, bIdx, bVal, cPtr, cCols, base, fill, maxBlocks);
-        break;
-    case SPGPU_TYPE_DOUBLE:
-        launchSpgemm<double>(s, cVal, entries, aRows, aPtr, aIdx, aVal, bPtr, bIdx, bVal, cPtr, cCols, base, fill, maxBlocks);
-        break;
-    case SPGPU_TYPE_COMPLEX_FLOAT:
-        launchSpgemm<cfloat>(s, cVal, entries, aRows, aPtr, aIdx, aVal, bPtr, bIdx, bVal, cPtr, cCols, base, fill, maxBlocks);
-        break;
-    default:
-        launchSpgemm<cdouble>(s, cVal, entries, aRows, aPtr, aIdx, aVal, bPtr, bIdx, bVal, cPtr, cCols, base, fill, maxBlocks);
-        break;
-    }
+    const bool launched = forValueType(type, [&](auto tag) {
+        if (entries > 0) {
+            const SpgemmWork w = carveSpgemm(const_cast<void*>(work), aRows, 0); /* the columns' place depends on aRows alone */
+            (void)hipMemcpyAsync(cCols, w.cCols, (size_t)entries * sizeof(int), hipMemcpyDeviceToDevice, s);
+        }
+        launchSpgemm<decltype(tag)>(s, cVal, entries, aRows, aPtr, aIdx, aVal, bPtr, bIdx, bVal, cPtr, cCols, base, fill, maxBlocks);
+    });
+    if (!launched)
+        return SPGPU_UNSUPPORTED;
     spgpuDebugCheck(handle, "csr spgemm");
     return SPGPU_SUCCESS;
 }
@@ -484,7 +420,7 @@ spgpuStatus_t spgpuCsrSpgemmPlanDevice(spgpuHandle_t handle, int* cNonZerosCount
         return SPGPU_SUCCESS;
     hipStream_t s = handle->currentStream;
     if (productsCount <= 0) {
-        hipLaunchKernelGGL(spgSetIntsKernel, dim3(gridFor((long long)aRowsCount + 1)), dim3(kCvThreads), 0, s, cRowPtr, (long long)aRowsCount + 1,
+        hipLaunchKernelGGL(csrSetIntsKernel, dim3(gridFor((long long)aRowsCount + 1)), dim3(kCvThreads), 0, s, cRowPtr, (long long)aRowsCount + 1,
                            baseIndex);
         spgpuDebugCheck(handle, "csr spgemm plan");
         return SPGPU_SUCCESS;
@@ -493,7 +429,7 @@ spgpuStatus_t spgpuCsrSpgemmPlanDevice(spgpuHandle_t handle, int* cNonZerosCount
         return SPGPU_UNSUPPORTED;
     const int n = productsCount;
     const SpgemmWork w = carveSpgemm(work, aRowsCount, (size_t)n);
-    const int rowBits = spgBitsFor(aRowsCount), colBits = spgBitsFor(bColumnsCount);
+    const int rowBits = bitsFor(aRowsCount), colBits = bitsFor(bColumnsCount);
     const int* unique = w.prodTotals + scanBlocks(n); /* the scan's grand total */
     int* host = static_cast<int*>(spgpuPrivate(handle)->reduceHost);
     size_t bytes = 0;
@@ -507,7 +443,7 @@ spgpuStatus_t spgpuCsrSpgemmPlanDevice(spgpuHandle_t handle, int* cNonZerosCount
     if (rocprim::radix_sort_keys(w.temp, bytes, (const SpgKey*)w.keysA, w.keysB, (size_t)n, 0u,
                                  (unsigned)(rowBits + colBits > 0 ? rowBits + colBits : 1), s) != hipSuccess)
         return SPGPU_UNSPECIFIED;
-    hipLaunchKernelGGL(spgHeadFlagsKernel, dim3(gridFor(n)), dim3(kCvThreads), 0, s, w.entryOf, (const SpgKey*)w.keysB, n);
+    hipLaunchKernelGGL(csrHeadFlagsKernel, dim3(gridFor(n)), dim3(kCvThreads), 0, s, w.entryOf, (const SpgKey*)w.keysB, n);
     exclusiveScan(s, w.entryOf, w.entryOf, (long long)n, 1, w.prodTotals);
     hipLaunchKernelGGL(spgColumnsKernel, dim3(gridFor(n)), dim3(kCvThreads), 0, s, w.cCols, (const int*)w.entryOf, (const SpgKey*)w.keysB, n,
                        (SpgKey)(((SpgKey)1 << colBits) - 1), baseIndex);

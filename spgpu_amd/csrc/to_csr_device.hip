@@ -38,6 +38,7 @@
  * operations execute in order, the wave barriers only keep the compiler from moving them.
  */
 #include "convert_scan.hip.h"
+#include "csr_host.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -57,7 +58,6 @@ constexpr int kToCsrReadSteps = kToCsrGroupRows * kToCsrChunk / kWave;    /* 8: 
 constexpr int kToCsrWritePasses = kToCsrGroupRows * kToCsrChunk / kWave;  /* 8: 4 rows x 16 entries per pass */
 constexpr int kToCsrColsPerStep = kWave / kToCsrGroupRows;                /* 2 */
 constexpr int kToCsrRowsPerPass = kWave / kToCsrChunk;                    /* 4 */
-constexpr unsigned kToCsrMaxBlocks = 1048576;                             /* as gridFor of the COO route */
 
 enum { SPGPU_TO_CSR_FILL_PLAIN = 0, SPGPU_TO_CSR_FILL_TRANSPOSE = 1 };
 constexpr int kToCsrDefaultFill = SPGPU_TO_CSR_FILL_TRANSPOSE;
@@ -278,13 +278,6 @@ __global__ __launch_bounds__(kToCsrThreads) void toCsrTransposeFillKernel(int* c
     }
 }
 
-static unsigned toCsrGridFor(long long items, int perBlock, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kToCsrMaxBlocks;
-    const long long blocks = (items + perBlock - 1) / perBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 static size_t toCsrWorkInts(int rows) { return alignUpCv(2 * (size_t)rows + scanBlocks(rows) + 2, 64); }
 
 static spgpuStatus_t toCsrRowPtr(spgpuHandle_t handle, int* csrRowPtr, int* nonZerosCount, int* maxRowSize, int csrBase,
@@ -310,7 +303,7 @@ static spgpuStatus_t toCsrRowPtr(spgpuHandle_t handle, int* csrRowPtr, int* nonZ
     (void)hipMemsetAsync(misc, 0, TO_CSR_MISC_INTS * sizeof(int), s);
     if (rIdx)
         (void)hipMemsetAsync(hits, 0, (size_t)rows * sizeof(int), s);
-    hipLaunchKernelGGL(toCsrLengthsKernel, dim3(toCsrGridFor(rows, kToCsrThreads, 4096)), dim3(kToCsrThreads), 0, s, lengths, hits, misc,
+    hipLaunchKernelGGL(toCsrLengthsKernel, dim3(cappedGrid(rows, kToCsrThreads, 4096)), dim3(kToCsrThreads), 0, s, lengths, hits, misc,
                        src, rS, rIdx, rows, slots);
     (void)hipMemcpyAsync(host, misc, TO_CSR_MISC_INTS * sizeof(int), hipMemcpyDeviceToHost, s);
     (void)hipStreamSynchronize(s);
@@ -321,7 +314,7 @@ static spgpuStatus_t toCsrRowPtr(spgpuHandle_t handle, int* csrRowPtr, int* nonZ
     if (host[TO_CSR_BAD] || total > (unsigned long long)(slots > 0 ? slots : 0))
         return SPGPU_UNSUPPORTED; /* with every matrix row named once and no more entries than slots, the sums below fit an int */
     exclusiveScan(s, csrRowPtr, lengths, (long long)rows, 1, totals);
-    hipLaunchKernelGGL(toCsrFinishKernel, dim3(csrBase ? toCsrGridFor(rows, kToCsrThreads, 4096) : 1u), dim3(kToCsrThreads), 0, s, csrRowPtr,
+    hipLaunchKernelGGL(toCsrFinishKernel, dim3(csrBase ? cappedGrid(rows, kToCsrThreads, 4096) : 1u), dim3(kToCsrThreads), 0, s, csrRowPtr,
                        rows, csrBase, (const int*)(totals + scanBlocks(rows)));
     (void)hipStreamSynchronize(s); /* `work` is the caller's again on return */
     spgpuDebugCheck(handle, "to-csr row pointers");
@@ -336,7 +329,7 @@ static void launchToCsrFill(hipStream_t s, int* csrCols, void* csrVals, const in
                             int maxBlocks)
 {
     if (fill == SPGPU_TO_CSR_FILL_PLAIN) {
-        hipLaunchKernelGGL(toCsrRowFillKernel<ELEM>, dim3(toCsrGridFor(rows, kToCsrThreads, maxBlocks)), dim3(kToCsrThreads), 0, s, csrCols,
+        hipLaunchKernelGGL(toCsrRowFillKernel<ELEM>, dim3(cappedGrid(rows, kToCsrThreads, maxBlocks)), dim3(kToCsrThreads), 0, s, csrCols,
                            static_cast<ELEM*>(csrVals), rowPtr, csrBase, static_cast<const ELEM*>(values), indices, src, rS, rIdx, rows,
                            srcBase);
         return;
@@ -345,7 +338,7 @@ static void launchToCsrFill(hipStream_t s, int* csrCols, void* csrVals, const in
     const int subsPerHack = hell ? (src.hackSize + kToCsrGroupRows - 1) / kToCsrGroupRows : 1;
     const long long hacks = hell ? ((long long)rows + src.hackSize - 1) / src.hackSize : ((long long)rows + kToCsrGroupRows - 1) / kToCsrGroupRows;
     const long long groups = hacks * subsPerHack;
-    hipLaunchKernelGGL(toCsrTransposeFillKernel<ELEM>, dim3(toCsrGridFor(groups, kToCsrWaves, maxBlocks)), dim3(kToCsrThreads), 0, s,
+    hipLaunchKernelGGL(toCsrTransposeFillKernel<ELEM>, dim3(cappedGrid(groups, kToCsrWaves, maxBlocks)), dim3(kToCsrThreads), 0, s,
                        csrCols, static_cast<ELEM*>(csrVals), rowPtr, csrBase, static_cast<const ELEM*>(values), indices, src, subsPerHack,
                        groups, rS, rIdx, rows, srcBase);
 }

@@ -15,7 +15,8 @@
  * Scratch (ints): misc[16] | level[rows] | listA[rows] | listB[rows] | pos[rows] | scan totals; misc[1] the bad-input flag,
  * misc[2] the rows left, misc[3] the levels so far, misc[4] a round that assigned nothing.
  *
- * THE SOLVES.  One thread per row, the row summed in storage order with contraction off (trsvRow), so both give the same bytes:
+ * THE SOLVES.  One thread per row, the row summed in storage order with contraction off (trsvRow, on exactSubMul and exactDiv of
+ * csr_shared.hip.h), so both give the same bytes:
  *   plain    (csrTrsvLevelKernel) one launch per level, grid-strided over the level's part of rowOrder;
  *   chained  (csrTrsvChainKernel) the host rule of trsv_rules.h cuts the level list into segments: a level of more than
  *            kTrsvChainWidth rows is a launch as in plain; a maximal run of narrower levels is ONE launch of ONE workgroup, which
@@ -26,7 +27,7 @@
  *            __syncthreads() is a workgroup-scope release and acquire over all address spaces, global memory included, which
  *            also keeps the compiler from moving a load of x across it.  No further fence.
  */
-#include "convert_scan.hip.h"
+#include "csr_shared.hip.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 #include "trsv_rules.h"
@@ -216,51 +217,6 @@ __global__ __launch_bounds__(kCvThreads) void trsvFinishKernel(int* rowOrder, in
     }
 }
 
-/* ---- the arithmetic of the contract ---- */
-/* acc - (a * x): the product rounded, then the difference; the pragma keeps hipcc, which contracts by default, from fusing them */
-__device__ inline float trsvSubMul(float acc, float a, float x)
-{
-#pragma clang fp contract(off)
-    const float p = a * x;
-    return acc - p;
-}
-__device__ inline double trsvSubMul(double acc, double a, double x)
-{
-#pragma clang fp contract(off)
-    const double p = a * x;
-    return acc - p;
-}
-template <typename R> __device__ inline Cx<R> trsvSubMul(Cx<R> acc, Cx<R> a, Cx<R> x)
-{
-#pragma clang fp contract(off)
-    const R rr = a.x * x.x, ii = a.y * x.y, ri = a.x * x.y, ir = a.y * x.x;
-    const R re = rr - ii, im = ri + ir;
-    const R outRe = acc.x - re, outIm = acc.y - im;
-    return Cx<R>{outRe, outIm};
-}
-/* n / d: one correctly rounded division (hipcc's default for fp32 too: no fast-math flag is passed) */
-__device__ inline float trsvDiv(float n, float d)
-{
-#pragma clang fp contract(off)
-    return n / d;
-}
-__device__ inline double trsvDiv(double n, double d)
-{
-#pragma clang fp contract(off)
-    return n / d;
-}
-/* the textbook quotient, every operation rounded separately; den may overflow or underflow (the header says so) */
-template <typename R> __device__ inline Cx<R> trsvDiv(Cx<R> n, Cx<R> d)
-{
-#pragma clang fp contract(off)
-    const R rr = d.x * d.x, ii = d.y * d.y;
-    const R den = rr + ii;
-    const R a = n.x * d.x, b = n.y * d.y, c = n.y * d.x, e = n.x * d.y;
-    const R top = a + b, bottom = c - e;
-    const R re = top / den, im = bottom / den;
-    return Cx<R>{re, im};
-}
-
 /* Row i of the contract.  x and b may be the same array: b[i] is read before x[i] is written, and no other row reads b[i]. */
 template <typename T>
 __device__ inline void trsvRow(T* x, const T* b, int i, const int* ptr, const int* idx, const T* val, int base, int side, int diag)
@@ -274,10 +230,10 @@ __device__ inline void trsvRow(T* x, const T* b, int i, const int* ptr, const in
             if (diag == SPGPU_TRSV_DIAG_STORED)
                 pivot = val[e];
         } else if (side == SPGPU_TRSV_LOWER ? j < i : j > i) {
-            acc = trsvSubMul(acc, val[e], x[j]);
+            acc = exactSubMul(acc, val[e], x[j]);
         }
     }
-    x[i] = diag == SPGPU_TRSV_DIAG_STORED ? trsvDiv(acc, pivot) : acc;
+    x[i] = diag == SPGPU_TRSV_DIAG_STORED ? exactDiv(acc, pivot) : acc;
 }
 
 /* plain: the `count` rows of one level, order[0, count) */
@@ -405,29 +361,15 @@ spgpuStatus_t spgpuCsrTrsvDeviceWith(spgpuHandle_t handle, void* x, const void* 
         solve = kTrsvDefaultSolve;
     if (solve != SPGPU_TRSV_SOLVE_PLAIN && solve != SPGPU_TRSV_SOLVE_CHAINED)
         return SPGPU_UNSUPPORTED;
-    if (valuesType != SPGPU_TYPE_FLOAT && valuesType != SPGPU_TYPE_DOUBLE && valuesType != SPGPU_TYPE_COMPLEX_FLOAT &&
-        valuesType != SPGPU_TYPE_COMPLEX_DOUBLE)
-        return SPGPU_UNSUPPORTED;
     if (!x || !b || !levelPtrHost || !trsvSideAndDiagKnown(side, diag))
         return SPGPU_UNSUPPORTED;
     hipStream_t s = handle->currentStream;
-#define SPGPU_TRSV_LAUNCH(T) \
-    launchCsrTrsv<T>(s, x, b, levelsCount, rowOrder, levelPtr, levelPtrHost, rowPtr, colIndices, values, baseIndex, side, diag, solve, maxBlocks)
-    switch (valuesType) {
-    case SPGPU_TYPE_FLOAT:
-        SPGPU_TRSV_LAUNCH(float);
-        break;
-    case SPGPU_TYPE_DOUBLE:
-        SPGPU_TRSV_LAUNCH(double);
-        break;
-    case SPGPU_TYPE_COMPLEX_FLOAT:
-        SPGPU_TRSV_LAUNCH(cfloat);
-        break;
-    default:
-        SPGPU_TRSV_LAUNCH(cdouble);
-        break;
-    }
-#undef SPGPU_TRSV_LAUNCH
+    const bool launched = forValueType(valuesType, [&](auto tag) {
+        launchCsrTrsv<decltype(tag)>(s, x, b, levelsCount, rowOrder, levelPtr, levelPtrHost, rowPtr, colIndices, values, baseIndex, side, diag,
+                                     solve, maxBlocks);
+    });
+    if (!launched)
+        return SPGPU_UNSUPPORTED;
     spgpuDebugCheck(handle, "csr trsv");
     return SPGPU_SUCCESS;
 }

@@ -24,6 +24,7 @@
  * The plain refill (csrValuesRowKernel), one thread per destination row, serves every hackSize that is no multiple of 32
  * (a group would be mostly idle lanes) and is the second implementation the tests compare bytes with.
  */
+#include "csr_host.h"
 #include "numeric.hip.h"
 #include "spgpu_internal.h"
 
@@ -41,7 +42,6 @@ constexpr int kUpChunk = 16;                                     /* slab columns
 constexpr int kUpTileLd = 36;                                    /* padded row count of the LDS tile */
 constexpr int kUpReadPasses = kUpGroupRows * kUpChunk / kWave;   /* 8: 4 rows x 16 entries per pass */
 constexpr int kUpRowsPerPass = kWave / kUpChunk;                 /* 4 */
-constexpr unsigned kUpMaxBlocks = 1048576;                       /* as the full fill */
 
 enum { SPGPU_UPDATE_FILL_PLAIN = 0, SPGPU_UPDATE_FILL_TRANSPOSE = 1 };
 
@@ -250,26 +250,19 @@ __global__ __launch_bounds__(kUpThreads) void invertRowOrderKernel(int* rowOf, c
     }
 }
 
-static unsigned upGridFor(long long items, int perBlock, int maxBlocks)
-{
-    const long long cap = maxBlocks > 0 ? (long long)maxBlocks : (long long)kUpMaxBlocks;
-    const long long blocks = (items + perBlock - 1) / perBlock;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 template <typename ELEM, bool TO_HELL>
 static void launchRefill(hipStream_t s, void* values, const UpSlabs& slabs, int rows, const int* rowPtr, const void* csrVals, int csrBase,
                          const int* rIdx, int fill, int maxBlocks)
 {
     if (fill == SPGPU_UPDATE_FILL_PLAIN) {
-        hipLaunchKernelGGL((csrValuesRowKernel<ELEM, TO_HELL>), dim3(upGridFor(rows, kUpThreads, maxBlocks)), dim3(kUpThreads), 0, s,
+        hipLaunchKernelGGL((csrValuesRowKernel<ELEM, TO_HELL>), dim3(cappedGrid(rows, kUpThreads, maxBlocks)), dim3(kUpThreads), 0, s,
                            static_cast<ELEM*>(values), slabs, rows, rowPtr, static_cast<const ELEM*>(csrVals), csrBase, rIdx);
         return;
     }
     const int subsPerHack = TO_HELL ? (slabs.hackSize + kUpGroupRows - 1) / kUpGroupRows : 1;
     const long long hacks = TO_HELL ? ((long long)rows + slabs.hackSize - 1) / slabs.hackSize : ((long long)rows + kUpGroupRows - 1) / kUpGroupRows;
     const long long groups = hacks * subsPerHack;
-    hipLaunchKernelGGL((csrValuesTransposeKernel<ELEM, TO_HELL>), dim3(upGridFor(groups, kUpWaves, maxBlocks)), dim3(kUpThreads), 0, s,
+    hipLaunchKernelGGL((csrValuesTransposeKernel<ELEM, TO_HELL>), dim3(cappedGrid(groups, kUpWaves, maxBlocks)), dim3(kUpThreads), 0, s,
                        static_cast<ELEM*>(values), slabs, subsPerHack, groups, rows, rowPtr, static_cast<const ELEM*>(csrVals), csrBase, rIdx);
 }
 
@@ -367,7 +360,7 @@ spgpuStatus_t spgpuInvertRowOrderDevice(spgpuHandle_t handle, int* rowOf, const 
 {
     if (rows <= 0)
         return SPGPU_SUCCESS;
-    hipLaunchKernelGGL(invertRowOrderKernel, dim3(upGridFor(rows, kUpThreads, 4096)), dim3(kUpThreads), 0, handle->currentStream, rowOf, rIdx,
+    hipLaunchKernelGGL(invertRowOrderKernel, dim3(cappedGrid(rows, kUpThreads, 4096)), dim3(kUpThreads), 0, handle->currentStream, rowOf, rIdx,
                        rows);
     spgpuDebugCheck(handle, "invert row order");
     return SPGPU_SUCCESS;

@@ -2,8 +2,11 @@
 """Is the device code of two builds of libspgpu.so the same?  Takes the gfx950 code objects out of each library's fat binary
 (one per translation unit), and compares, kernel by kernel over the union of all of them: the set of kernel symbols, every
 kernel's instruction stream (llvm-objdump -d without addresses and encodings; branches print as relative offsets, so the text
-does not depend on where a kernel sits) and its resource note (VGPRs, SGPRs, LDS, scratch, kernarg size).
-usage: tools/device_code_diff.py OLD/libspgpu.so NEW/libspgpu.so   (exit status 1 if anything differs)"""
+does not depend on where a kernel sits) and its resource note (VGPRs, SGPRs, LDS, scratch, kernarg size).  The fill between a
+kernel's last instruction and the next kernel or the end of the section (s_nop 0 or zero words, which the disassembler prints under
+the kernel in front of them) is not compared: it depends on which kernel comes next, not on the kernel.
+usage: tools/device_code_diff.py OLD/libspgpu.so NEW/libspgpu.so [-v] [OLDSYMBOL=NEWSYMBOL ...]   (exit status 1 if anything
+differs; a kernel that was renamed is compared under its new name)"""
 import os
 import re
 import struct
@@ -13,6 +16,7 @@ import tempfile
 
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+FILL = ("s_nop 0", "v_cndmask_b32_e32 v0, s0, v0, vcc", "...")  # the second is how a zero word disassembles
 NOTE_KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "kernarg_segment_size")
 
 
@@ -52,6 +56,8 @@ def kernels_of(library):
             for line in listing.split("\n") + ["<end>:"]:
                 label = re.match(r"^<?([^\s<>]+)>?:$", line.strip()) if not line.startswith((" ", "\t")) else None
                 if label:
+                    while lines and lines[-1] in FILL:
+                        lines.pop()
                     if name in resources:
                         found.setdefault(name, []).append(("\n".join(lines), resources[name]))  # (a template: one per unit)
                         compared += 1
@@ -67,8 +73,11 @@ def kernels_of(library):
 
 def main():
     old, new = kernels_of(sys.argv[1]), kernels_of(sys.argv[2])
+    for was, now in (arg.split("=") for arg in sys.argv[3:] if "=" in arg):
+        old.setdefault(now, []).extend(old.pop(was))
+        print(f"renamed: {was} -> {now}")
     gone, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
-    differ = [k for k in sorted(set(old) & set(new)) if old[k] != new[k]]
+    differ = [k for k in sorted(set(old) & set(new)) if set(old[k]) != set(new[k])]  # a kernel of a header: a copy per unit
     instructions = sum(len(text.split("\n")) for copies in new.values() for text, _ in copies)
     print(f"kernels compared: {len(set(old) & set(new))} (old {len(old)}, new {len(new)}); {instructions} instructions in the new build")
     print(f"compared per kernel: instruction stream, {', '.join(NOTE_KEYS)}")
