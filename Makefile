@@ -49,12 +49,12 @@ $(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 # Plain-C callers of the C ABI (gcc, no hipcc): the reference's ctest.c / hellPerf.cpp / diaPerf.cpp flows, three CG solvers,
 # a Jacobi-preconditioned one, CG on an HDIA matrix, the device-side transpose of a HELL matrix, the way back to CSR / CSC,
 # new coefficients for a stored HELL matrix, the assembly of a finite-element listing, a Galerkin coarse operator, the
-# system matrix M + dt K of a time step, CG preconditioned by symmetric Gauss-Seidel, and the second level of an aggregation
-# multigrid.
+# system matrix M + dt K of a time step, CG preconditioned by symmetric Gauss-Seidel, the second level of an aggregation
+# multigrid, and the same Gauss-Seidel CG on a multicolour order.
 TOOLS := tools/ctest_amd.bin tools/hellperf_amd.bin tools/diaperf_amd.bin tools/cg_amd.bin tools/cg_ragged_amd.bin \
          tools/cg_multi_amd.bin tools/pcg_amd.bin tools/cg_hdia_amd.bin tools/transpose_amd.bin tools/to_csr_amd.bin \
          tools/update_amd.bin tools/assemble_amd.bin tools/galerkin_amd.bin tools/timestep_amd.bin tools/gs_amd.bin \
-         tools/amg_setup_amd.bin
+         tools/amg_setup_amd.bin tools/multicolour_amd.bin
 tools: lib $(TOOLS)
 tools/%.bin: tools/%.c $(HDRS) $(LIBDIR)/libspgpu.so
 	gcc -O2 -std=gnu99 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude $< -L$(LIBDIR) -lspgpu -L$(ROCM)/lib -lamdhip64 -lm \

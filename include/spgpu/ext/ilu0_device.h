@@ -7,6 +7,7 @@
  * below the diagonal, U on and above it -- which is the layout the triangular solve reads from one array with two plans.  The
  * factorisation is an ANALYSIS of the pattern, once (spgpuCsrIlu0PlanDevice), and a pass over the values at every new set of
  * coefficients (spgpuCsrIlu0Device), which can sit in a captured graph in front of the two solves.
+ * The number of levels belongs to the row order: spgpu/ext/colour_device.h reorders a matrix so that it has about as many as colours.
  *
  * All array arguments are DEVICE pointers unless marked host.  Every call runs on handle->currentStream.
  *

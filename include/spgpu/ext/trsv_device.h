@@ -59,6 +59,7 @@
  *   - the Plan returns host data and therefore synchronises the stream -- once per sweep of its analysis, so about once per
  *     level: it is set-up code, and on a matrix of many thousands of levels (a bidiagonal one has rowsCount of them) it takes
  *     that many round trips;
+ *   - the number of levels belongs to the row order: spgpu/ext/colour_device.h reorders a matrix so that it has about as many as colours;
  *   - the solve never synchronises, allocates nothing and keeps no state.  It reads levelPtrHost at call time, which is also
  *     capture time: its launches can be captured into a HIP graph and replayed after b and values changed in place;
  *   - no kernel of the Plan or of the solve waits for another workgroup: levels are ordered by stream order between launches

@@ -395,6 +395,24 @@ spgpuCsrAggregateDeviceWith = _bind("spgpuCsrAggregateDeviceWith", i32, spgpuCsr
 spgpuCsrStrengthDeviceWith = _bind("spgpuCsrStrengthDeviceWith", i32, spgpuCsrStrengthDevice.argtypes + [i32, i32])
 csr_aggregate_default_shape = _bind("spgpuCsrAggregateDefaultShape", i32, [i32, i32])
 
+# ---- ext/colour_device.h: multicolour ordering on CSR arrays -- colouring, order, symmetric permutation -- in HBM ---------------------
+spgpuCsrColourWorkBytes = _decl("spgpuCsrColourWorkBytes", C.c_size_t, [i32])
+# (handle, &coloursCount, &roundsCount, colourOf, rows, rowPtr, colIndices, baseIndex, work)
+spgpuCsrColourDevice = _decl("spgpuCsrColourDevice", i32, [Handle, C.POINTER(i32), C.POINTER(i32), ptr, i32, ptr, ptr, i32, ptr])
+# (handle, order, inverse, colourPtr, rows, coloursCount, colourOf, work)
+spgpuCsrColourOrderDevice = _decl("spgpuCsrColourOrderDevice", i32, [Handle, ptr, ptr, ptr, i32, i32, ptr, ptr])
+spgpuCsrPermuteWorkBytes = _decl("spgpuCsrPermuteWorkBytes", C.c_size_t, [i32])
+# (handle, bRowPtr, bColIndices, bValues, rows, order, inverse, aRowPtr, aColIndices, aValues, baseIndex, valuesType, work)
+spgpuCsrPermuteDevice = _decl("spgpuCsrPermuteDevice", i32, [Handle, ptr, ptr, ptr, i32, ptr, ptr, ptr, ptr, ptr, i32, i32, ptr])
+# not in the headers: the row shapes behind the calls above, for the A/B tool and the tests that compare them
+# (..., shape, maxBlocks): shape COLOUR_SHAPE_THREAD (one thread per row), a power of two in [2, 64] (that many lanes of one wavefront
+# per row) or <= 0 for the public call's choice -- csr_colour_default_shape(rows, nnz) for the colouring, one fixed shape for the
+# permutation, which cannot read nnz without a synchronise; maxBlocks > 0 caps the grids
+COLOUR_SHAPE_THREAD = 1
+spgpuCsrColourDeviceWith = _bind("spgpuCsrColourDeviceWith", i32, spgpuCsrColourDevice.argtypes + [i32, i32])
+spgpuCsrPermuteDeviceWith = _bind("spgpuCsrPermuteDeviceWith", i32, spgpuCsrPermuteDevice.argtypes + [i32, i32])
+csr_colour_default_shape = _bind("spgpuCsrColourDefaultShape", i32, [i32, i32])
+
 
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -612,6 +612,65 @@ def csr_tentative(aggregate_of, candidate, base, dtype):
     return (np.arange(n_rows + 1, dtype=np.int32) + np.int32(base)), aggregate_of + np.int32(base), vals
 
 
+def csr_colour(row_ptr, col, base, priority=None):
+    """(colours, rounds, colour_of) as include/spgpu/ext/colour_device.h defines them, restated round by round.  N(i) is the columns
+    j != i of row i's stored entries; the tuple of node i is (hash(i), i) in one 64-bit word; every node starts with colour -1.  A
+    round reads c0 and writes c1: an uncoloured i is ready if every j in N(i) has c0[j] >= 0 or a smaller tuple, and a ready i takes
+    the smallest c >= 0 that is no c0[j], j in N(i); every other node keeps c0[i].  Rounds repeat until nobody is uncoloured.
+    ValueError on what spgpuCsrColourDevice refuses: a column outside the matrix.  `priority` replaces hash(i) (uint64 below 2**31):
+    for tests that compare priorities, not a parameter of the device call."""
+    n_rows, ptr, col, row_of = _square_csr(row_ptr, col, base)
+    if np.any((col < 0) | (col >= n_rows)):
+        raise ValueError("a column lies outside the matrix")
+    keep = col != row_of
+    src, dst = row_of[keep], col[keep]
+    tuples = ((aggregate_priority(n_rows) if priority is None else np.asarray(priority, np.uint64)) << np.uint64(32)) \
+        | np.arange(n_rows, dtype=np.uint64)
+    colour = np.full(n_rows, -1, np.int64)
+    rounds = 0
+    while np.any(colour < 0):
+        c0 = colour
+        waits = np.zeros(n_rows, bool)                                # an uncoloured neighbour with a larger tuple
+        waits[src[(c0[dst] < 0) & (tuples[dst] > tuples[src])]] = True
+        ready = (c0 < 0) & ~waits
+        taken = ready[src] & (c0[dst] >= 0)                           # (node, a colour one of its neighbours holds), each pair once
+        pairs = np.unique(src[taken] * np.int64(n_rows + 1) + c0[dst[taken]])
+        node, held = pairs // (n_rows + 1), pairs % (n_rows + 1)
+        first = np.searchsorted(node, node, side="left")
+        rank = np.arange(pairs.size) - first                          # the held colours of a node ascend: the first gap is free
+        free = np.bincount(node, minlength=n_rows).astype(np.int64)   # no gap: the number of colours held
+        np.minimum.at(free, node[held != rank], rank[held != rank])
+        colour = np.where(ready, free, c0)
+        rounds += 1
+    return (int(colour.max()) + 1 if n_rows > 0 else 0), rounds, colour.astype(np.int32)
+
+
+def csr_colour_order(colour_of, colours):
+    """(order, inverse, colour_ptr) of include/spgpu/ext/colour_device.h: the 0-based rows by (colour, row) ascending,
+    inverse[order[k]] = k, and colour_ptr[c] = the number of rows of colours < c for c <= colours."""
+    colour_of = np.asarray(colour_of, np.int64)
+    n_rows = colour_of.size
+    order = np.lexsort((np.arange(n_rows), colour_of))
+    inverse = np.empty(n_rows, np.int64)
+    inverse[order] = np.arange(n_rows)
+    colour_ptr = np.searchsorted(colour_of[order], np.arange(colours + 1), side="left")
+    return order.astype(np.int32), inverse.astype(np.int32), colour_ptr.astype(np.int32)
+
+
+def csr_permute(order, inverse, a_ptr, a_cols, a_vals, base):
+    """(b_ptr, b_cols, b_vals) of B = A(order, order) as include/spgpu/ext/colour_device.h defines it: row k of B is row order[k] of
+    A, a stored column j becomes inverse[j - base] + base, a row's entries ascend by new column, equal columns in A's storage
+    order; the values are moved, not computed."""
+    n_rows, ptr, col, row_of = _square_csr(a_ptr, a_cols, base)
+    order, inverse = np.asarray(order, np.int64), np.asarray(inverse, np.int64)
+    vals = np.ascontiguousarray(np.asarray(a_vals)[:ptr[-1]])
+    b_ptr = np.zeros(n_rows + 1, np.int64)
+    b_ptr[1:] = np.cumsum(np.diff(ptr)[order])
+    new_row, new_col = inverse[row_of], inverse[col]
+    at = np.lexsort((np.arange(col.size), new_col, new_row))
+    return (b_ptr + base).astype(np.int32), (new_col[at] + base).astype(np.int32), vals[at].copy()
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
