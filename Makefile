@@ -50,11 +50,11 @@ $(BUILD)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 # a Jacobi-preconditioned one, CG on an HDIA matrix, the device-side transpose of a HELL matrix, the way back to CSR / CSC,
 # new coefficients for a stored HELL matrix, the assembly of a finite-element listing, a Galerkin coarse operator, the
 # system matrix M + dt K of a time step, CG preconditioned by symmetric Gauss-Seidel, the second level of an aggregation
-# multigrid, and the same Gauss-Seidel CG on a multicolour order.
+# multigrid, the same Gauss-Seidel CG on a multicolour order, and multicolour Gauss-Seidel sweeps as a solver.
 TOOLS := tools/ctest_amd.bin tools/hellperf_amd.bin tools/diaperf_amd.bin tools/cg_amd.bin tools/cg_ragged_amd.bin \
          tools/cg_multi_amd.bin tools/pcg_amd.bin tools/cg_hdia_amd.bin tools/transpose_amd.bin tools/to_csr_amd.bin \
          tools/update_amd.bin tools/assemble_amd.bin tools/galerkin_amd.bin tools/timestep_amd.bin tools/gs_amd.bin \
-         tools/amg_setup_amd.bin tools/multicolour_amd.bin
+         tools/amg_setup_amd.bin tools/multicolour_amd.bin tools/sweep_amd.bin
 tools: lib $(TOOLS)
 tools/%.bin: tools/%.c $(HDRS) $(LIBDIR)/libspgpu.so
 	gcc -O2 -std=gnu99 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude $< -L$(LIBDIR) -lspgpu -L$(ROCM)/lib -lamdhip64 -lm \

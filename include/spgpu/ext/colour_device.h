@@ -9,7 +9,8 @@
  * order.  Rows of one colour do not depend on each other, so on B the Plans that already exist find about as many levels as there
  * are colours.  Correctness of a solve never rests on the colouring: the Plans still derive the levels from the stored
  * dependencies.  A poor colouring costs levels, not answers.  A multicolour order usually costs a preconditioned solver
- * iterations; tools/multicolour_amd.c prints both sides of that trade.
+ * iterations; tools/multicolour_amd.c prints both sides of that trade.  spgpu/ext/sweep_device.h relaxes on A itself with this
+ * colouring, one launch per colour, and there the colouring does carry correctness: its Plan checks it.
  *
  * All array arguments are DEVICE pointers unless marked host.  Every call runs on handle->currentStream.
  *

@@ -3,9 +3,10 @@
  * The sparse triangular solve x = T^-1 * b on CSR arrays, level-scheduled on the device (the reference solves no triangular
  * system, and neither did this library).
  *
- * NEW: the whole of Gauss-Seidel and SSOR, as a smoother on the hierarchy that spgpu/ext/spgemm_device.h and
- * spgpu/ext/add_device.h build and as a preconditioner that is stronger than the diagonal of spgpu/ext/precond.h, and the
- * application half of every ILU(0) or IC(0), wherever the factor came from (ext/ilu0_device.h makes the ILU(0)).  T is one
+ * NEW: Gauss-Seidel and SSOR applied to a zero initial guess, that is, as a preconditioner that is stronger than the diagonal of
+ * spgpu/ext/precond.h, on the matrices that spgpu/ext/spgemm_device.h and spgpu/ext/add_device.h build, and the application half
+ * of every ILU(0) or IC(0), wherever the factor came from (ext/ilu0_device.h makes the ILU(0)).  The solve computes T^-1 * b and
+ * nothing else: a sweep with a guess, x <- (D + L)^-1 * (b - U * x), as a smoother needs it, is spgpu/ext/sweep_device.h.  T is one
  * triangle of a matrix A that is given WHOLE: (D + L)^-1 and (D + U)^-1 come from A's own arrays, and an ILU(0) stored in A's
  * pattern (unit L below, U on and above the diagonal) is solved from one array with two plans.  The solve is an ANALYSIS of the
  * dependencies, once (spgpuCsrTrsvPlanDevice: the level of every row, the rows listed level by level), and a pass over the

@@ -413,6 +413,34 @@ spgpuCsrColourDeviceWith = _bind("spgpuCsrColourDeviceWith", i32, spgpuCsrColour
 spgpuCsrPermuteDeviceWith = _bind("spgpuCsrPermuteDeviceWith", i32, spgpuCsrPermuteDevice.argtypes + [i32, i32])
 csr_colour_default_shape = _bind("spgpuCsrColourDefaultShape", i32, [i32, i32])
 
+# ---- ext/sweep_device.h: multicolour Gauss-Seidel / SOR sweeps in place and the residual r = b - A x on CSR arrays, in HBM ------------
+SWEEP_FORWARD, SWEEP_BACKWARD, SWEEP_SYMMETRIC = 0, 1, 2
+spgpuCsrSweepWorkBytes = _decl("spgpuCsrSweepWorkBytes", C.c_size_t, [i32])
+# (handle, &entriesCount, diagPos, colourPtrHost (host), rows, coloursCount, order or NULL, colourPtr, colourOf, rowPtr, colIndices,
+#  baseIndex, work)
+spgpuCsrSweepPlanDevice = _decl("spgpuCsrSweepPlanDevice", i32, [Handle, C.POINTER(i32), ptr, C.POINTER(i32), i32, i32, ptr, ptr, ptr, ptr, ptr,
+                                                                i32, ptr])
+# (handle, x, b, rows, coloursCount, order or NULL, colourPtrHost (host), diagPos, rowPtr, colIndices, values, baseIndex, direction,
+#  omega (host, one element, or NULL), valuesType, entriesCount)
+spgpuCsrSweepDevice = _decl("spgpuCsrSweepDevice", i32, [Handle, ptr, ptr, i32, i32, ptr, C.POINTER(i32), ptr, ptr, ptr, ptr, i32, i32, ptr, i32,
+                                                        i32])
+# (handle, r, b, x, rows, rowPtr, colIndices, values, baseIndex, valuesType, entriesCount)
+spgpuCsrResidualDevice = _decl("spgpuCsrResidualDevice", i32, [Handle, ptr, ptr, ptr, i32, ptr, ptr, ptr, i32, i32, i32])
+# not in the headers: the row shapes and segmentings behind the calls above, for the A/B tool and the tests that compare them
+# (..., shape, solve, maxBlocks) and (..., shape, maxBlocks): shape SWEEP_SHAPE_THREAD (one thread per row), a power of two in [2, 64]
+# (that many lanes of one wavefront per row) or <= 0 for the public call's choice, csr_sweep_default_shape(rows, nnz); solve
+# TRSV_SOLVE_PLAIN (one launch per colour), TRSV_SOLVE_CHAINED (a run of colours of at most SWEEP_CHAIN_WIDTH rows each is one launch
+# of one workgroup per SWEEP_CHAIN_PASSES colours) or < 0 for the public call's choice; maxBlocks > 0 caps a grid-strided launch
+SWEEP_SHAPE_THREAD = 1
+spgpuCsrSweepDeviceWith = _bind("spgpuCsrSweepDeviceWith", i32, spgpuCsrSweepDevice.argtypes + [i32, i32, i32])
+spgpuCsrResidualDeviceWith = _bind("spgpuCsrResidualDeviceWith", i32, spgpuCsrResidualDevice.argtypes + [i32, i32])
+csr_sweep_default_shape = _bind("spgpuCsrSweepDefaultShape", i32, [i32, i32])
+SWEEP_SOLVE_DEFAULT = _bind("spgpuCsrSweepDefaultSolve", i32, [])()
+SWEEP_CHAIN_WIDTH = _bind("spgpuCsrSweepChainWidth", i32, [])()
+SWEEP_CHAIN_PASSES = _bind("spgpuCsrSweepChainPasses", i32, [])()
+# (colourPtrHost (host), coloursCount, direction, solve) -> the launches of one sweep call
+csr_sweep_launches = _bind("spgpuCsrSweepLaunches", i32, [C.POINTER(i32), i32, i32, i32])
+
 
 # ---- oell_device.h (new: rows ordered by length in HBM) + the host order (ell_conv.h) ----------------------------
 oellOrder = _decl("oellOrder", None, [ptr, ptr, ptr, i32, i32, i32])

@@ -671,6 +671,130 @@ def csr_permute(order, inverse, a_ptr, a_cols, a_vals, base):
     return (b_ptr + base).astype(np.int32), (new_col[at] + base).astype(np.int32), vals[at].copy()
 
 
+def csr_sweep_plan(row_ptr, col, base, colours, colour_ptr, colour_of=None, order=None):
+    """(diag_pos, colour_ptr_host, entries) as include/spgpu/ext/sweep_device.h defines them: diag_pos[i] the 0-based position of
+    entry (i, i), the colours + 1 ints of colour_ptr, and row_ptr[rows] - base.  With `order` the colour of node k is colour_of[k];
+    without one it is the c with colour_ptr[c] <= k < colour_ptr[c + 1] and colour_of is not read.  ValueError on what
+    spgpuCsrSweepPlanDevice refuses: a column outside the matrix, a row without its diagonal or with two, a colour_of outside
+    [0, colours) under an order, a stored off-diagonal entry between two nodes of one colour, a colour_ptr that does not start at 0,
+    descends or does not end at the number of rows."""
+    n_rows, ptr, col, row_of = _square_csr(row_ptr, col, base)
+    colour_ptr = np.asarray(colour_ptr, np.int64)[:colours + 1]
+    if n_rows > 0 and (colours < 1 or colour_ptr.size != colours + 1 or colour_ptr[0] != 0 or colour_ptr[-1] != n_rows
+                       or np.any(np.diff(colour_ptr) < 0)):
+        raise ValueError("colour_ptr does not describe the rows")
+    if col.size and (col.min() < 0 or col.max() >= n_rows):
+        raise ValueError("a column lies outside the matrix")
+    diagonal = col == row_of
+    counts = np.bincount(row_of[diagonal], minlength=n_rows)
+    if np.any(counts == 0):
+        raise ValueError("a row stores no diagonal")
+    if np.any(counts > 1):
+        raise ValueError("a row stores its diagonal twice")
+    if order is not None:
+        colour = np.asarray(colour_of, np.int64)[:n_rows]
+        if np.any(colour < 0) or np.any(colour >= colours):
+            raise ValueError("a colour lies outside [0, colours)")
+    else:
+        colour = np.searchsorted(colour_ptr, np.arange(n_rows), side="right") - 1
+    if np.any(colour[row_of[~diagonal]] == colour[col[~diagonal]]):
+        raise ValueError("a stored entry joins two nodes of one colour")
+    return np.flatnonzero(diagonal).astype(np.int32), colour_ptr.astype(np.int32), int(ptr[-1])
+
+
+def _parts_of(a, dtype):
+    """A contiguous copy of `a` as rows of its real parts (one part for a real type, two for a complex one) and the part type."""
+    part = dtype if dtype.kind != "c" else np.dtype("f%d" % (dtype.itemsize // 2))
+    return np.ascontiguousarray(a).copy().view(part).reshape(-1, 1 if dtype.kind != "c" else 2), part
+
+
+def _sub_products(acc, v, x, ptr, col, i, skip):
+    """acc - the sum of a_e * x[col_e] over row i in storage order, position `skip` left out: every product rounded (six operations
+    for complex), then the difference, in the part type's own scalar arithmetic."""
+    real = len(acc) == 1
+    for e in range(ptr[i], ptr[i + 1]):
+        if e == skip:
+            continue
+        j = col[e]
+        if real:
+            product = v[e, 0] * x[j, 0]
+            acc = [acc[0] - product]
+        else:
+            ar, ai, xr, xi = v[e, 0], v[e, 1], x[j, 0], x[j, 1]
+            rr, ii, ri, ir = ar * xr, ai * xi, ar * xi, ai * xr
+            re, im = rr - ii, ri + ir
+            acc = [acc[0] - re, acc[1] - im]
+    return acc
+
+
+def csr_sweep(row_ptr, col, vals, b, x, base, colours, colour_ptr_host, diag_pos, order=None, direction=capi.SWEEP_FORWARD, omega=None):
+    """x after one spgpuCsrSweepDevice as include/spgpu/ext/sweep_device.h defines it (a new array), restated with the element type's
+    own scalar arithmetic, one operation at a time.  For every colour of the direction and every row i of it: acc = b_i; for each
+    stored entry but the one at diag_pos[i], in storage order, acc = acc - (a_e * x[col_e]); g = acc / a_ii; x_i = g without omega,
+    else d = g - x_i and x_i = x_i + (omega * d).  Complex goes through its real parts as in csr_trsv.  SYMMETRIC is the forward
+    list and then the backward list.  One Python step per stored entry: a restatement for tests, not a tool."""
+    n_rows, ptr, col, _ = _square_csr(row_ptr, col, base)
+    vals, b, x = np.asarray(vals), np.asarray(b), np.asarray(x)
+    dtype = vals.dtype
+    if b.dtype != dtype or x.dtype != dtype:
+        raise ValueError("the matrix, b and x hold different types")
+    real = dtype.kind != "c"
+    v, part = _parts_of(vals, dtype)
+    rhs, _ = _parts_of(b[:n_rows], dtype)
+    out, _ = _parts_of(x[:n_rows], dtype)
+    w = None if omega is None else _parts_of(np.array([omega], dtype), dtype)[0][0]
+    cp = np.asarray(colour_ptr_host, np.int64)
+    passes = {capi.SWEEP_FORWARD: list(range(colours)), capi.SWEEP_BACKWARD: list(range(colours - 1, -1, -1)),
+              capi.SWEEP_SYMMETRIC: list(range(colours)) + list(range(colours - 1, -1, -1))}[direction]
+    with np.errstate(all="ignore"):
+        for c in (passes if n_rows > 0 else []):
+            for t in range(cp[c], cp[c + 1]):
+                i = int(order[t]) if order is not None else t
+                d = int(diag_pos[i])
+                acc = _sub_products([rhs[i, p] for p in range(len(rhs[i]))], v, out, ptr, col, i, d)
+                if real:
+                    g = [acc[0] / v[d, 0]]
+                else:
+                    (nr, ni), (dr, di) = acc, (v[d, 0], v[d, 1])
+                    rr, ii = dr * dr, di * di
+                    den = rr + ii
+                    a, bb, cc, dd = nr * dr, ni * di, ni * dr, nr * di
+                    top, bottom = a + bb, cc - dd
+                    g = [top / den, bottom / den]
+                if w is not None:
+                    mine = [out[i, p] for p in range(len(g))]
+                    diff = [g[p] - mine[p] for p in range(len(g))]
+                    if real:
+                        product = w[0] * diff[0]
+                        g = [mine[0] + product]
+                    else:
+                        rr, ii, ri, ir = w[0] * diff[0], w[1] * diff[1], w[0] * diff[1], w[1] * diff[0]
+                        re, im = rr - ii, ri + ir
+                        g = [mine[0] + re, mine[1] + im]
+                for p in range(len(g)):
+                    out[i, p] = g[p]
+    return out.reshape(-1).view(dtype)
+
+
+def csr_residual(row_ptr, col, vals, b, x, base):
+    """r = b - A * x as include/spgpu/ext/sweep_device.h defines it: r_i starts as b_i and every stored entry of row i, the diagonal
+    included, is subtracted in storage order, the product rounded and then the difference.  An empty row moves b_i's bits."""
+    n_rows, ptr, col, _ = _square_csr(row_ptr, col, base)
+    vals, b, x = np.asarray(vals), np.asarray(b), np.asarray(x)
+    dtype = vals.dtype
+    if b.dtype != dtype or x.dtype != dtype:
+        raise ValueError("the matrix, b and x hold different types")
+    v, _ = _parts_of(vals, dtype)
+    r, _ = _parts_of(b[:n_rows], dtype)
+    xs, _ = _parts_of(x, dtype)
+    with np.errstate(all="ignore"):
+        for i in range(n_rows):
+            acc = _sub_products([r[i, p] for p in range(r.shape[1])], v, xs, ptr, col, i, -1)
+            for p in range(len(acc)):
+                r[i, p] = acc[p]
+    return r.reshape(-1).view(dtype)
+
+
 def hell_transpose_device(handle, cM, rP, hack_offsets, rS, r_idx, n_rows, n_cols, hack_size, base, slots, letter, t_hack_size=32,
                           t_base=0, ell_pitches=None):
     """HELL (or, with ell_pitches = (values pitch, indices pitch), ELL) arrays in HBM -> the HELL arrays of A^T in HBM, through
